@@ -33,6 +33,14 @@ keeps round 1's independent streams per rank.  Run directly, `bench.py --gpus N`
 Clock pre-heat: a cold MI355X needs ~1 s of load before its clocks settle (20 timed steps are 6 ms);
 the SAME launch is therefore repeated for --preheat-s seconds (default 2.0, reported as `preheat_s`)
 before the W warm-up and K timed steps.  steps / warmup are exactly what the command line says.
+
+A plain run measures the headline only.  `--full` adds everything else the line used to carry: the CPU baseline
+(`cpu_baseline`), the cfg3 / cfg4 side entries (`side`) and, with --gpus N > 1, the RCCL per-layer baseline and the
+per-phase timings of the step (`rccl_per_layer_baseline`, `tp_phases`).
+
+`--dump-outputs DIR`: after the timed steps, what the timed path computed in its last step is written as DIR/<name>.npy
+(float32; at most 64 MB in all, beyond that a fixed, seeded sample of every array).  The inputs depend on the arguments
+only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -48,6 +56,21 @@ sys.path.insert(0, REPO)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 TRAFFIC_PROFILE = os.path.join("profiles", "traffic_r06.json")
+DUMP_MAX_BYTES = 60_000_000      # --dump-outputs payload: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as <dirname>/<name><suffix>.npy in float32.  Above DUMP_MAX_BYTES
+    in all, every array is cut to a fixed, seeded sample of its flattened elements (the same positions in every run with the same
+    arguments), in proportion to its size."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    for name, v in host.items():
+        if total > DUMP_MAX_BYTES:
+            k = max(1, v.size * DUMP_MAX_BYTES // total)
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, k, replace=False))]
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 def build_base_layers(n_distinct, N, K, low_frac, seed0):
@@ -201,7 +224,8 @@ def side_layers(workload, dev, synth_mode):
     return layers, M
 
 
-def measure_side(workload, steps, warmup, preheat_s, gemm_backend="default", small_batch_image="default", synth_mode="oracle"):
+def measure_side(workload, steps, warmup, preheat_s, gemm_backend="default", small_batch_image="default", synth_mode="oracle",
+                 dump_dir=None):
     """--workload cfg3 | cfg4: the other single-GPU configurations of BASELINE.json, as bench lines of their own (`--workload`)
     and, compact, under "side" in the driver's default line (round 6).  One step = one pass over the
     configuration's linears through the modules' forward with the LIBRARY'S DEFAULTS, timed with HIP events on torch's current
@@ -236,8 +260,7 @@ def measure_side(workload, steps, warmup, preheat_s, gemm_backend="default", sma
     alg = sum(l.packed.algorithmic_bytes(M) for l in layers)
 
     def run():
-        for l, x in zip(layers, x_of):
-            l(x)
+        return [l(x) for l, x in zip(layers, x_of)]
 
     try:
         with torch.no_grad():
@@ -252,12 +275,15 @@ def measure_side(workload, steps, warmup, preheat_s, gemm_backend="default", sma
             t0 = time.perf_counter()
             e0.record()
             for _ in range(steps):
-                run()
+                last = run()
             e1.record()
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
     finally:
         Q.GEMM_BACKEND, Q.SMALL_BATCH_IMAGE = old
+    if dump_dir:
+        dump_outputs(dump_dir, {f"y{i:02d}": y for i, y in enumerate(last)})
+        del last
     dev_s = e0.elapsed_time(e1) * 1e-3 / steps
     same_box = {}
     if workload == "cfg3" and gemm_backend in ("auto", "fused"):
@@ -330,7 +356,8 @@ def measure_side(workload, steps, warmup, preheat_s, gemm_backend="default", sma
 
 
 def run_side_workload(a):
-    print(json.dumps(measure_side(a.workload, a.steps, a.warmup, a.preheat_s, a.gemm_backend, a.small_batch_image, a.synth)), flush=True)
+    print(json.dumps(measure_side(a.workload, a.steps, a.warmup, a.preheat_s, a.gemm_backend, a.small_batch_image, a.synth,
+                                  a.dump_outputs)), flush=True)
 
 
 def side_summary(budget_note="library defaults, device-synthesised layers (the product's GPU producer), own pre-heat + HIP events"):
@@ -376,7 +403,12 @@ def main():
     ap.add_argument("--M", type=int, default=1)
     ap.add_argument("--low-frac", type=float, default=0.9)
     ap.add_argument("--mode", choices=["grouped", "graph", "eager"], default="grouped")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the cfg3 / cfg4 side entries and, with "
+                         "--gpus N > 1, the RCCL per-layer baseline and the per-phase timings of the step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--parallel", choices=["auto", "dp", "tp"], default="auto",
                     help="auto: tp when --gpus > 1; tp: LLaMA tensor-parallel mapping of the layer stream + one "
                          "all-reduce of the K-split partial outputs per step (strong scaling); dp: independent "
@@ -399,7 +431,7 @@ def main():
                          "configs[2] / configs[3] as side lines (see run_side_workload)")
     ap.add_argument("--synth", choices=["oracle", "device"], default="oracle",
                     help="cfg3 / cfg4: where the layers' structure comes from (see side_layers); the driver line's \"side\" entries use device")
-    ap.add_argument("--no-side", action="store_true", help="default workload: skip the cfg3 / cfg4 side entries of the line")
+    ap.add_argument("--no-side", action="store_true", help="default workload with --full: skip the cfg3 / cfg4 side entries of the line")
     ap.add_argument("--gemm-backend", choices=["default", "auto", "tuned", "library", "fused"], default="default",
                     help="cfg3: quant.GEMM_BACKEND -- default = the library's own setting (\"auto\": always the hand-written kernel over each "
                          "layer's GEMM image, round 5); tuned = round 4's routing (library GEMM where the 128 x 256 tiles leave a thin last "
@@ -521,7 +553,8 @@ def main():
                 want = "per-layer"
 
         def step_tp(path, record=False):
-            """one step on `path`: 'fused' | 'p2p-per-layer' | 'p2p-stacked' | 'rccl-per-layer' | 'rccl-stacked'"""
+            """one step on `path`: 'fused' | 'p2p-per-layer' | 'p2p-stacked' | 'rccl-per-layer' | 'rccl-stacked'; returns this rank's
+            outputs (its rows of the N-split layers, the summed K-split layers)"""
             if record:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -533,7 +566,7 @@ def main():
                 for pk, xk, yk in zip(gk.packed, gk.x, yk16):
                     if not comm.fused_linear_(pk, None, xk, yk):
                         raise SystemExit("--tp-collectives fused: the K-split shard is not one GEMV pass")
-                return
+                return {"y_nsplit": gn.y, "y_ksplit": yk16}
             gk.launch()
             if record:
                 e1.record()
@@ -544,6 +577,7 @@ def main():
                     comm.all_reduce_(t)
                 else:
                     base_all_reduce(t)
+            return {"y_nsplit": gn.y, "y_ksplit": gk.y}
 
         # reference sums through the baseline collective, once
         gk.launch()
@@ -583,16 +617,15 @@ def main():
     fused_tp = tp_path == "fused"
 
     def step(record=False):
+        """one step; returns its outputs, name -> list of per-layer tensors"""
         if tp:
             return step_tp(tp_path, record)
         if a.mode == "grouped":
-            for g, _ in groups:
-                g.launch()
-        else:
-            for m, x in singles:
-                m(x)
+            return {"y": groups[0][0].launch()}          # one group unless tp
+        return {"y": [m(x) for m, x in singles]}
 
     def capture(fn):
+        """(graph, the outputs the captured step writes on every replay)"""
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -601,20 +634,20 @@ def main():
         torch.cuda.synchronize()
         gr = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gr):
-            fn()
-        return gr
+            outs = fn()
+        return gr, outs
 
-    graph = None
+    graph, graph_outs = None, None
     tp_graphed = False
     if a.mode == "graph" and not tp:
-        graph = capture(step)
+        graph, graph_outs = capture(step)
         run = graph.replay
     elif fused_tp and a.tp_graph:
         # the whole step in ONE hipGraph: the call number of the push / reduce pair lives in the peers' buffers, so a replay advances
         # it like an eager call.  A failed capture is agreed over the group (all ranks replay, or all ranks launch eagerly).
         ok = 1
         try:
-            graph = capture(step)
+            graph, graph_outs = capture(step)
         except (RuntimeError, _lib.PblError) as e:
             tp_notes.append(f"hipGraph capture of the fused step failed ({str(e)[:100]}): eager launches")
             ok, graph = 0, None
@@ -648,8 +681,10 @@ def main():
     preheat_s = time.perf_counter() - t_pre if a.preheat_s > 0 else 0.0
 
     def timed(run_fn, record):
-        """W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; max over the ranks"""
+        """W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; max over the ranks.  Also returns the
+        last step's outputs (a graph replay returns none: the captured step's buffers hold them)"""
         kev.clear()
+        last = None
         for _ in range(a.warmup):
             run_fn()
         torch.cuda.synchronize()
@@ -661,9 +696,9 @@ def main():
         e0.record()
         for _ in range(a.steps):
             if record:
-                step(True)
+                last = step(True)
             else:
-                run_fn()
+                last = run_fn()
         e1.record()
         torch.cuda.synchronize()
         if use_dist:
@@ -676,10 +711,15 @@ def main():
             tt = torch.tensor([wall_, dev_, kern_], device=ctl, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             wall_, dev_, kern_ = tt.tolist()
-        return wall_, dev_, kern_
+        return wall_, dev_, kern_, (last if last is not None else graph_outs)
+
+    def dump(outs):
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {k: torch.stack(v) for k, v in outs.items()}, f"_rank{rank}" if world > 1 else "")
 
     rec = tp and not tp_graphed
-    wall, dev_s, kern_s = timed(run, rec)
+    wall, dev_s, kern_s, outs = timed(run, rec)
+    dump(outs)
     tp_valid_after = None
     if tp and comm is not None and tp_path != "rccl-per-layer" and not tp_path.startswith("rccl"):
         # a peer wait that timed out poisons the sums with NaN and sets the buffer's status word: the number above would describe a
@@ -692,11 +732,12 @@ def main():
             ok = 0
         tp_valid_after = bool(agree_min(ok, None, dev))
     rccl_base = None
-    if tp and (tp_path != "rccl-per-layer") and (backend == "nccl" or os.environ.get("PBL_BENCH_BASELINE") == "1"):
+    if tp and (tp_path != "rccl-per-layer") and (backend == "nccl" or os.environ.get("PBL_BENCH_BASELINE") == "1") and \
+            (a.full or tp_valid_after is False):
         # the baseline north_star names, timed the same way OUTSIDE the K steps reported above: GEMV launches + one RCCL all-reduce per
-        # K-split layer (64 eager 16 KB collectives per step)
+        # K-split layer (64 eager 16 KB collectives per step).  A plain run times it only to replace a broken exchange's number.
         main_path, tp_path = tp_path, "rccl-per-layer"
-        bw, bd, bk = timed(step, True)
+        bw, bd, bk, bouts = timed(step, True)
         tp_path = main_path
         rccl_base = {"value": a.layers * a.M * a.steps / bw, "unit": "layer-tokens/s", "ms_per_step": 1e3 * bw / a.steps,
                      "us_per_step_device": 1e6 * bd / a.steps, "collective_us_per_step": 1e6 * (bd - bk) / a.steps,
@@ -705,9 +746,10 @@ def main():
         if tp_valid_after is False:
             tp_notes.append(f"{main_path} reported a timed-out peer wait: the line carries the RCCL per-layer measurement")
             wall, dev_s, kern_s, tp_path, tp_graphed = bw, bd, bk, "rccl-per-layer", False
+            dump(bouts)
 
     tp_phases = None
-    if tp:
+    if tp and a.full:
         # where a step's time goes, per phase, from a few EAGER steps of the path that was timed (outside the K steps above; round 6,
         # VERDICT r5 item 9): the N-split launch, and per K-split layer the push GEMV + reduce kernel (fused), or the GEMV launch + the
         # all-reduce calls (per-layer / stacked paths); HIP events on the launch stream, max over ranks
@@ -823,9 +865,9 @@ def main():
                 out["rccl_per_layer_baseline"] = rccl_base
             if tp_phases is not None:
                 out["tp_phases"] = tp_phases
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline([b["W"] for b in base], a.K, a.M)
-        if world == 1 and not a.no_side and a.mode == "grouped":
+        if a.full and world == 1 and not a.no_side and a.mode == "grouped":
             # BASELINE configs[2] / configs[3] measured by the SAME process the driver times (after the headline: its numbers are
             # final above; the stream's blobs are released first)
             groups.clear()

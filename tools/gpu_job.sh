@@ -27,16 +27,16 @@ case $MODE in
 validate)
   for i in $(seq 1 ${REPS:-2}); do timeout 1500 python -m pytest tests -q -m gpu -p no:cacheprovider --timeout 900 > $O/pytest$i.txt 2>&1; tail -3 $O/pytest$i.txt | cut -c1-300; grep -E "^(FAILED|ERROR)" $O/pytest$i.txt | cut -c1-300; done
   timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3
-  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; line $O/bench_driver.json
+  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; line $O/bench_driver.json
   timeout 300 python bench.py --workload cfg4 --steps 20 --warmup 5 > $O/cfg4.json 2> $O/cfg4.err; line $O/cfg4.json
   timeout 300 python bench.py --workload cfg3 --steps 10 --warmup 3 > $O/cfg3.json 2> $O/cfg3.err; line $O/cfg3.json
   timeout 200 python tools/bench_host.py > $O/host.json 2> $O/host.err; cut -c1-700 $O/host.json
   for n in 2 4; do
-    PBL_BENCH_BACKEND=gloo PBL_BENCH_BASELINE=1 MASTER_PORT=296$n timeout 400 python bench.py --gpus $n --steps 5 --warmup 2 --preheat-s 0.3 --no-cpu-baseline > $O/tp${n}_plumbing.json 2> $O/tp${n}_plumbing.err
+    PBL_BENCH_BACKEND=gloo PBL_BENCH_BASELINE=1 MASTER_PORT=296$n timeout 400 python bench.py --gpus $n --steps 5 --warmup 2 --preheat-s 0.3 --no-cpu-baseline --full > $O/tp${n}_plumbing.json 2> $O/tp${n}_plumbing.err
     echo tp$n rc=$?; line $O/tp${n}_plumbing.json
   done ;;
 plumbing8)
-  PBL_BENCH_BACKEND=gloo PBL_BENCH_BASELINE=1 MASTER_PORT=2968 timeout 500 python bench.py --gpus 8 --steps 5 --warmup 2 --preheat-s 0.3 --no-cpu-baseline > $O/tp8_plumbing.json 2> $O/tp8_plumbing.err
+  PBL_BENCH_BACKEND=gloo PBL_BENCH_BASELINE=1 MASTER_PORT=2968 timeout 500 python bench.py --gpus 8 --steps 5 --warmup 2 --preheat-s 0.3 --no-cpu-baseline --full > $O/tp8_plumbing.json 2> $O/tp8_plumbing.err
   echo tp8 rc=$?; line $O/tp8_plumbing.json ;;
 gemm)
   PBL_BENCH_SHAPES=5120x5120:0.95,5120x13824:0.95,13824x5120:0.95,11008x4096:0.95 timeout 600 python tools/bench_gemm.py > $O/gemm_13b.jsonl 2> $O/gemm_13b.err; cut -c1-420 $O/gemm_13b.jsonl

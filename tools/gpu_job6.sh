@@ -6,13 +6,13 @@ MODE=${1:-quick}; O=gpurun_out/${2:-r6}; mkdir -p $O
 timeout 300 python __graft_entry__.py > $O/build.txt 2>&1; tail -1 $O/build.txt
 case $MODE in
 bench)   # the driver's command (with the side entries)
-  T0=$(date +%s.%N); timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench wall $(echo "$(date +%s.%N) - $T0" | bc) s"; tail -2 $O/bench_driver.err | cut -c1-300
+  T0=$(date +%s.%N); timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench wall $(echo "$(date +%s.%N) - $T0" | bc) s"; tail -2 $O/bench_driver.err | cut -c1-300
   python tools/show_line.py $O/bench_driver.json
   ;;
 quick)   # the round's new tests, smoke, the driver's command (with the side entries)
   timeout 1200 python -m pytest tests -q -m gpu -p no:cacheprovider --timeout 900 -k "${KEXPR:-full_tensor or beyond_fp16 or split_and_join}" > $O/pytest_new.txt 2>&1; tail -3 $O/pytest_new.txt | cut -c1-300; grep -E "^(FAILED|ERROR)" $O/pytest_new.txt | cut -c1-300
   timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3
-  T0=$(date +%s.%N); timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench wall $(echo "$(date +%s.%N) - $T0" | bc) s"; tail -2 $O/bench_driver.err | cut -c1-300
+  T0=$(date +%s.%N); timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench wall $(echo "$(date +%s.%N) - $T0" | bc) s"; tail -2 $O/bench_driver.err | cut -c1-300
   python tools/show_line.py $O/bench_driver.json
   ;;
 small)   # the small-batch kernel's geometries: parity tests, then a sweep of forced plans per shape (tools/bench_small.py)
@@ -71,7 +71,7 @@ mix2)   # x-staging byte-reduction ablations of the GEMM-image kernel; tensor-pa
   done
   unset PBL_LIB
   for n in 2 4; do
-    PBL_BENCH_BACKEND=gloo PBL_BENCH_BASELINE=1 MASTER_PORT=296$n timeout 500 python bench.py --gpus $n --steps 5 --warmup 2 --preheat-s 0.3 --no-cpu-baseline > $O/tp${n}_plumbing.json 2> $O/tp${n}_plumbing.err
+    PBL_BENCH_BACKEND=gloo PBL_BENCH_BASELINE=1 MASTER_PORT=296$n timeout 500 python bench.py --gpus $n --steps 5 --warmup 2 --preheat-s 0.3 --no-cpu-baseline --full > $O/tp${n}_plumbing.json 2> $O/tp${n}_plumbing.err
     echo tp$n rc=$?; python - $O/tp${n}_plumbing.json <<'P'
 import json,sys
 for l in open(sys.argv[1]):
@@ -105,7 +105,7 @@ profcfg3)   # rocprofv3 of the cfg3 side workload alone (kernel trace + one SQ c
   python tools/summarize_prof.py gpurun_out/prof_r06_cfg3 > gpurun_out/prof_r06_cfg3/summary.txt 2>&1; cut -c1-300 gpurun_out/prof_r06_cfg3/summary.txt | head -24
   grep '"metric"' gpurun_out/prof_r06_cfg3/trace.log | cut -c1-600
   find gpurun_out/prof_r06_cfg3 -name "*.db" -size +6M -delete
-  T0=$(date +%s.%N); timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench wall $(echo "$(date +%s.%N) - $T0" | bc) s"
+  T0=$(date +%s.%N); timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench wall $(echo "$(date +%s.%N) - $T0" | bc) s"
   python tools/show_line.py $O/bench_driver.json
   ;;
 full)
