@@ -472,6 +472,24 @@ int pbl_gemv_f16_fused(const pbl_layer* layers_dev, const uint64_t* y_off_dev, c
 int pbl_gemv_f16_fused_host(const pbl_layer* layers_host, const uint64_t* y_off_host, const void* x, void* y, int L, int M,
                             uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32, void* stream);
 
+/* Decode prologues of a LLaMA decoder layer (fp16 activations, group-free layers, one GEMV pass): the GEMV's staging phase builds
+ * the multiplied row from the layer's raw tensors, so the small torch kernels between two launches disappear.
+ *   pbl_gemv_f16_fused_norm_host  pbl_gemv_f16_fused_host on LlamaRMSNorm(x): x [M, K] is the UN-normalised hidden state, norm_w
+ *                                 [K] fp16 the norm's weight, norm_eps its variance_epsilon.  Staged per token: fp16(w[k] * fp16(x[k] * r)),
+ *                                 r = 1 / sqrt(sum(x^2) / K + eps) in fp32 (IEEE sqrt and divide) -- HF's order of roundings; inf / NaN
+ *                                 in a row give HF's NaN row.  Every member has in_features K.
+ *   pbl_linear_f16_swiglu         y [M, N] = layer(silu(gate) * up) for gate_up [M, ldx] fp16: gate at columns [0, K), up at [up_off,
+ *                                 up_off + K) (up_off >= K, ldx >= up_off + K) -- the fused gate/up launch's output.  Staged:
+ *                                 fp16(fp16(silu(g)) * u), silu in fp32 as g / (1 + exp(-g)): F.silu and `*` on half tensors.
+ * PBL_ERR_UNSUPPORTED (as pbl_linear_bf16): column groups, more rows than one pass takes under the GEMV's LDS budget (e.g. M = 4 at
+ * K = 11008), a row count the matrix-core kernel serves -- the caller runs the unfused composition.  PBL_ERR_INVALID_ARG for bad
+ * pointers or sizes.  Neither synchronises nor allocates: both can be captured in a hipGraph. */
+int pbl_gemv_f16_fused_norm_host(const pbl_layer* layers_host, const uint64_t* y_off_host, const void* x, void* y, int L, int M,
+                                 uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32,
+                                 const void* norm_w, float norm_eps, void* stream);
+int pbl_linear_f16_swiglu(const pbl_layer* layer, const void* gate_up, uint32_t ldx, uint32_t up_off, void* y, int M, int y_f32,
+                          void* stream);
+
 /* ---------------- QAT step, weight side ------------------------------------------ */
 /* The elementwise work of one training step of BinaryXnorExceptOutliersLinear
  * (quant/outlier_quantizer.py:83-99; straight-through estimator quant/quantizer.py:18-25), fused into

@@ -229,7 +229,15 @@ struct GemvArgs {
     // multiplies the result back and writes bf16 (fp32 when y_f32).  A token holding inf / NaN runs as its indicator row with scale
     // +inf.  Exactly the arithmetic of pbl_act_bf16_prepare + the fp16 kernel + pbl_act_finish (csrc/pbl_act.hip), in ONE launch.
     int x_bf16;
+    // x prologues (XP; pbl_gemv_f16_fused_norm_host / pbl_linear_f16_swiglu): the staging phase builds the multiplied row from the
+    // decoder layer's raw tensors.  RMSNorm: x is the hidden state, norm_w [K] fp16 the norm's weight.  SwiGLU: x is a [M, ldx]
+    // matrix whose row holds gate at column 0 and up at column up_off.  (At the END of the struct: no kernarg offset moves.)
+    const _Float16* norm_w;
+    float norm_eps;
+    uint32_t ldx;
+    uint32_t up_off;
 };
+enum { XP_NONE = 0, XP_RMSNORM = 1, XP_SWIGLU = 2 };
 
 // Gather 8 fp16 values from LDS byte addresses a[0..7] into 4 packed half2 registers
 // (entry 2p in the low half, 2p+1 in the high half).  All loads are in flight and waited
@@ -334,14 +342,33 @@ __device__ __forceinline__ uint32_t bf16_to_scaled_f16(uint32_t b, bool finite, 
     return uint32_t(__builtin_bit_cast(uint16_t, _Float16(r)));
 }
 
+// HF's SwiGLU on half tensors, one element: F.silu (fp32 opmath, g / (1 + exp(-g)), one rounding to fp16), then `*` (the product of
+// two fp16 values is exact in fp32: one rounding).  +-inf / NaN propagate as torch's do.
+__device__ __forceinline__ uint32_t swiglu_f16(uint32_t gb, uint32_t ub) {
+    const float g = float(__builtin_bit_cast(_Float16, uint16_t(gb)));
+    const _Float16 s = _Float16(g / (1.0f + expf(-g)));
+    const _Float16 r = _Float16(float(s) * float(__builtin_bit_cast(_Float16, uint16_t(ub))));
+    return uint32_t(__builtin_bit_cast(uint16_t, r));
+}
+// HF's LlamaRMSNorm, one element of an fp16 row with normaliser r: fp16(g * fp16(x * r)) -- normalise in fp32, round to the input
+// dtype, multiply by the fp16 weight (exact in fp32), round once.
+__device__ __forceinline__ uint32_t rmsnorm_f16(uint32_t xb, uint32_t gb, float r) {
+    const _Float16 h = _Float16(float(__builtin_bit_cast(_Float16, uint16_t(xb))) * r);
+    const _Float16 o = _Float16(float(__builtin_bit_cast(_Float16, uint16_t(gb))) * float(h));
+    return uint32_t(__builtin_bit_cast(uint16_t, o));
+}
+
 // XB: bf16 activations converted in the staging phase, bf16 result (GemvArgs.x_bf16).  A template parameter, not a run-time branch:
-// the fp16 instantiations -- the headline kernel among them -- are the code they were.
-template <int MB, int WPB, bool SF, int SPLIT, bool XB = false>
+// the fp16 instantiations -- the headline kernel among them -- are the code they were.  XP (x prologue, fp16 only): XP_RMSNORM stages
+// LlamaRMSNorm(x) (pass 1: every token's sum of squares, one barrier, pass 2: the normalised row), XP_SWIGLU stages silu(gate) * up.
+template <int MB, int WPB, bool SF, int SPLIT, bool XB = false, int XP = XP_NONE>
 __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void pbl_gemv_kernel(GemvArgs args) {
     static_assert(SPLIT == 1 || SPLIT == WPB, "split mode uses every wave of the workgroup on one record");
+    static_assert(!(XB && XP != XP_NONE), "the x prologues take fp16 activations");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ uint32_t s_amax[XB ? MB * WPB : 1];           // XB: per (token, wave) the largest |x| bit pattern
     __shared__ float s_tscale[XB ? MB : 1];                  //     per token the power of two (or +inf) the result is multiplied with
+    __shared__ float s_ssq[XP == XP_RMSNORM ? MB * WPB : 1]; // XP_RMSNORM: per (token, wave) the partial sum of squares
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -490,6 +517,89 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
             } else {
                 for (int i = tid; i < K; i += nthr)
                     reinterpret_cast<uint16_t*>(xs)[m * xstride + i] = uint16_t(bf16_to_scaled_f16(xb[size_t(m) * K + i], finite, down));
+            }
+            for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
+        }
+    } else if constexpr (XP == XP_RMSNORM) {
+        // LlamaRMSNorm.forward on an fp16 row: pass 1 sums x^2 in fp32 (x^2 of an fp16 value is exact), one partial per (token, wave),
+        // one barrier; pass 2 re-reads the row and the weight (L1 / L2) and writes fp16(g * fp16(x * r)), r = 1 / sqrt(mean + eps)
+        // with an IEEE sqrt and divide.  mean = sum * (1 / K) as torch's mean kernel scales.  inf / NaN in a row: r = 0 or NaN, as HF.
+        const int nthr = WPB * PBL_WAVE;
+        const uint16_t* xb = reinterpret_cast<const uint16_t*>(xg);
+        const uint16_t* gw = reinterpret_cast<const uint16_t*>(args.norm_w);
+        const bool vec = (K & 7) == 0 && ((reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(gw)) & 15) == 0;
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+            float ss = 0.f;
+            if (vec) {
+                const u32x4* src = reinterpret_cast<const u32x4*>(xb + size_t(m) * K);
+                for (int i = tid; i < (K >> 3); i += nthr) {
+                    const u32x4 v = src[i];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float lo = float(__builtin_bit_cast(_Float16, uint16_t(v[j] & 0xFFFFu)));
+                        const float hi = float(__builtin_bit_cast(_Float16, uint16_t(v[j] >> 16)));
+                        ss = fmaf(lo, lo, ss);
+                        ss = fmaf(hi, hi, ss);
+                    }
+                }
+            } else {
+                for (int i = tid; i < K; i += nthr) {
+                    const float f = float(xg[size_t(m) * K + i]);
+                    ss = fmaf(f, f, ss);
+                }
+            }
+            ss = wave_sum(ss);
+            if (lane == 0) s_ssq[m * WPB + wave] = ss;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+            float ss = 0.f;
+#pragma unroll
+            for (int w = 0; w < WPB; ++w) ss += s_ssq[m * WPB + w];
+            const float r = 1.0f / sqrtf(ss * (1.0f / float(K)) + args.norm_eps);
+            if (vec) {
+                const u32x4* src = reinterpret_cast<const u32x4*>(xb + size_t(m) * K);
+                const u32x4* gsrc = reinterpret_cast<const u32x4*>(gw);
+                u32x4* dst = reinterpret_cast<u32x4*>(xs + m * xstride);
+                for (int i = tid; i < (K >> 3); i += nthr) {
+                    const u32x4 v = src[i], g = gsrc[i];
+                    u32x4 o;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        o[j] = rmsnorm_f16(v[j] & 0xFFFFu, g[j] & 0xFFFFu, r) | (rmsnorm_f16(v[j] >> 16, g[j] >> 16, r) << 16);
+                    dst[i] = o;
+                }
+            } else {
+                for (int i = tid; i < K; i += nthr)
+                    reinterpret_cast<uint16_t*>(xs)[m * xstride + i] = uint16_t(rmsnorm_f16(xb[size_t(m) * K + i], gw[i], r));
+            }
+            for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
+        }
+    } else if constexpr (XP == XP_SWIGLU) {
+        // silu(gate) * up from the fused gate/up launch's output: row m holds gate at [0, K) and up at [up_off, up_off + K)
+        const int nthr = WPB * PBL_WAVE;
+        const uint16_t* xb = reinterpret_cast<const uint16_t*>(xg);
+        const size_t ldx = args.ldx;
+        const uint32_t uo = args.up_off;
+        const bool vec = (K & 7) == 0 && (reinterpret_cast<uintptr_t>(xb) & 15) == 0 && (ldx & 7) == 0 && (uo & 7) == 0;
+        for (int m = 0; m < MB; ++m) {
+            if (vec) {
+                const u32x4* gsrc = reinterpret_cast<const u32x4*>(xb + size_t(m) * ldx);
+                const u32x4* usrc = reinterpret_cast<const u32x4*>(xb + size_t(m) * ldx + uo);
+                u32x4* dst = reinterpret_cast<u32x4*>(xs + m * xstride);
+                for (int i = tid; i < (K >> 3); i += nthr) {
+                    const u32x4 g = gsrc[i], u = usrc[i];
+                    u32x4 o;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        o[j] = swiglu_f16(g[j] & 0xFFFFu, u[j] & 0xFFFFu) | (swiglu_f16(g[j] >> 16, u[j] >> 16) << 16);
+                    dst[i] = o;
+                }
+            } else {
+                for (int i = tid; i < K; i += nthr)
+                    reinterpret_cast<uint16_t*>(xs)[m * xstride + i] = uint16_t(swiglu_f16(xb[size_t(m) * ldx + i], xb[size_t(m) * ldx + uo + i]));
             }
             for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
         }
@@ -722,18 +832,22 @@ size_t lds_bytes(uint32_t P, uint32_t max_nch, int mb, int wpb, int split = 1) {
     return s + 16;
 }
 
-template <int MB, int WPB, bool SF, int SPLIT = 1>
+template <int MB, int WPB, bool SF, int SPLIT = 1, int XP = XP_NONE>
 int launch(const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-    auto k = a.x_bf16 ? pbl_gemv_kernel<MB, WPB, SF, SPLIT, true> : pbl_gemv_kernel<MB, WPB, SF, SPLIT, false>;
+    void (*k)(GemvArgs);
+    if constexpr (XP != XP_NONE) k = pbl_gemv_kernel<MB, WPB, SF, SPLIT, false, XP>;     // (x prologues: fp16 only)
+    else k = a.x_bf16 ? pbl_gemv_kernel<MB, WPB, SF, SPLIT, true> : pbl_gemv_kernel<MB, WPB, SF, SPLIT, false>;
     // the bf16 instantiation holds s_amax / s_tscale in STATIC LDS on top of the dynamic size (4 MB (WPB + 1) bytes, rounded up):
     // both limits are on the sum (a layer just under a limit failed the launch instead of answering UNSUPPORTED, which
-    // pbl_linear_bf16's callers turn into the three-launch form)
-    const size_t stat = a.x_bf16 ? ((size_t(4) * MB * (WPB + 1) + 15) & ~size_t(15)) + 16 : 16;
+    // pbl_linear_bf16's callers turn into the three-launch form); the RMSNorm prologue holds s_ssq (4 MB WPB bytes) the same way
+    const size_t stat = a.x_bf16 ? ((size_t(4) * MB * (WPB + 1) + 15) & ~size_t(15)) + 16
+                      : XP == XP_RMSNORM ? ((size_t(4) * MB * WPB + 15) & ~size_t(15)) + 16 : 16;
+    const bool declines = a.x_bf16 || XP != XP_NONE;             // callers that have an unfused form to fall back to
     if (lds + stat > 64 * 1024) {
         if (lds + stat > 160 * 1024) return PBL_ERR_UNSUPPORTED;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 int(lds)) != hipSuccess)
-            return a.x_bf16 ? PBL_ERR_UNSUPPORTED : PBL_ERR_LAUNCH;
+            return declines ? PBL_ERR_UNSUPPORTED : PBL_ERR_LAUNCH;
     }
     GemvArgs args = a;
     void* argv[] = {&args};
@@ -1129,36 +1243,36 @@ int grouped_groups(const GemvArgs& a, int M, uint32_t max_NRB, uint32_t max_K, u
     return PBL_OK;
 }
 
-template <int WPB, bool SF>
+template <int WPB, bool SF, int XP = XP_NONE>
 int launch_mb2(int mb, const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
     switch (mb) {
-        case 1: return launch<1, WPB, SF>(a, grid, lds, st);
-        case 2: return launch<2, WPB, SF>(a, grid, lds, st);
-        case 3: return launch<3, WPB, SF>(a, grid, lds, st);
-        case 4: return launch<4, WPB, SF>(a, grid, lds, st);
+        case 1: return launch<1, WPB, SF, 1, XP>(a, grid, lds, st);
+        case 2: return launch<2, WPB, SF, 1, XP>(a, grid, lds, st);
+        case 3: return launch<3, WPB, SF, 1, XP>(a, grid, lds, st);
+        case 4: return launch<4, WPB, SF, 1, XP>(a, grid, lds, st);
         default: return PBL_ERR_INVALID_ARG;
     }
 }
-template <int WPB>
+template <int WPB, int XP = XP_NONE>
 int launch_mb(int mb, bool sf, const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-    return sf ? launch_mb2<WPB, true>(mb, a, grid, lds, st) : launch_mb2<WPB, false>(mb, a, grid, lds, st);
+    return sf ? launch_mb2<WPB, true, XP>(mb, a, grid, lds, st) : launch_mb2<WPB, false, XP>(mb, a, grid, lds, st);
 }
 // latency mode: S waves per record
-template <int S>
+template <int S, int XP = XP_NONE>
 int launch_split(int mb, bool sf, const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
     if (sf) {
         switch (mb) {
-            case 1: return launch<1, S, true, S>(a, grid, lds, st);
-            case 2: return launch<2, S, true, S>(a, grid, lds, st);
-            case 3: return launch<3, S, true, S>(a, grid, lds, st);
-            case 4: return launch<4, S, true, S>(a, grid, lds, st);
+            case 1: return launch<1, S, true, S, XP>(a, grid, lds, st);
+            case 2: return launch<2, S, true, S, XP>(a, grid, lds, st);
+            case 3: return launch<3, S, true, S, XP>(a, grid, lds, st);
+            case 4: return launch<4, S, true, S, XP>(a, grid, lds, st);
         }
     } else {
         switch (mb) {
-            case 1: return launch<1, S, false, S>(a, grid, lds, st);
-            case 2: return launch<2, S, false, S>(a, grid, lds, st);
-            case 3: return launch<3, S, false, S>(a, grid, lds, st);
-            case 4: return launch<4, S, false, S>(a, grid, lds, st);
+            case 1: return launch<1, S, false, S, XP>(a, grid, lds, st);
+            case 2: return launch<2, S, false, S, XP>(a, grid, lds, st);
+            case 3: return launch<3, S, false, S, XP>(a, grid, lds, st);
+            case 4: return launch<4, S, false, S, XP>(a, grid, lds, st);
         }
     }
     return PBL_ERR_INVALID_ARG;
@@ -1322,6 +1436,37 @@ int pbl_linear_bf16(const pbl_layer* layer, const void* x_bf16, void* y, int M, 
     }
 }
 
+// LLaMA's MLP tail in ONE launch: y [M, N] = down_proj(silu(gate) * up), the GEMV's staging phase building its x row from the fused
+// gate/up launch's output (gate_up [M, ldx] fp16: gate at column 0, up at column up_off) with torch's roundings (swiglu_f16).  One
+// GEMV pass of a group-free layer, like pbl_linear_bf16: PBL_ERR_UNSUPPORTED otherwise (column groups, more rows than one pass
+// takes, every row count route_of sends to the matrix-core kernel) -- the caller then runs silu and * in torch and the layer.
+int pbl_linear_f16_swiglu(const pbl_layer* layer, const void* gate_up, uint32_t ldx, uint32_t up_off, void* y, int M, int y_f32,
+                          void* stream) {
+    if (!layer || !layer->blob || !gate_up || !y || M < 1 || up_off < layer->K || uint64_t(ldx) < uint64_t(up_off) + layer->K)
+        return PBL_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
+    if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
+    const Route r = route_of(layer, M, true);
+    if (M > r.mb_max) return PBL_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool sf = layer->flags & PBL_FLAG_SAL_F16;
+    GemvArgs a{};
+    a.layer = *layer;
+    a.x = static_cast<const _Float16*>(gate_up);
+    a.y = y;
+    a.M = M; a.y_f32 = y_f32; a.grouped = 0;
+    a.ldx = ldx; a.up_off = up_off;
+    const int split = r.split, wpb = r.wpb;
+    const dim3 grid(split > 1 ? layer->NRB : (layer->NRB + wpb - 1) / wpb, 1, 1);
+    const size_t lds = lds_bytes(layer->P, layer->max_nch, M, wpb, split);
+    switch (split) {
+        case 8: return launch_split<8, XP_SWIGLU>(M, sf, a, grid, lds, st);
+        case 4: return launch_split<4, XP_SWIGLU>(M, sf, a, grid, lds, st);
+        case 2: return launch_split<2, XP_SWIGLU>(M, sf, a, grid, lds, st);
+        default: return wpb == 4 ? launch_mb<4, XP_SWIGLU>(M, sf, a, grid, lds, st) : launch_mb<1, XP_SWIGLU>(M, sf, a, grid, lds, st);
+    }
+}
+
 // K-split tensor parallelism, fused: the GEMV of this rank's column shard with its epilogue pushing the fp32 partial y[M, N]
 // straight into slot [set][rank] of every rank's peer-mapped communication buffer (pbl_comm_alloc / pbl_ipc_open; layout in
 // csrc/pbl_p2p_layout.h) -- 7 xGMI stores + 1 local per row owner -- and counting every finished record at the peers.
@@ -1418,6 +1563,7 @@ int pbl_gemv_f16_grouped(const pbl_layer* layers_dev, const void* const* x_dev, 
 }
 
 static int fused_launch(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream);
+static int fused_launch_norm(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream);
 
 int pbl_gemv_f16_fused(const pbl_layer* layers_dev, const uint64_t* y_off_dev, const void* x, void* y, int Lc, int M,
                        uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32, void* stream) {
@@ -1431,11 +1577,26 @@ int pbl_gemv_f16_fused(const pbl_layer* layers_dev, const uint64_t* y_off_dev, c
 }
 
 static int fused_host(const pbl_layer* layers_host, const uint64_t* y_off_host, const void* x, void* y, int Lc, int M,
-                      uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32, int x_bf16, void* stream);
+                      uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32, int x_bf16, void* stream,
+                      const void* norm_w = nullptr, float norm_eps = 0.f);
 
 int pbl_gemv_f16_fused_host(const pbl_layer* layers_host, const uint64_t* y_off_host, const void* x, void* y, int Lc, int M,
                             uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32, void* stream) {
     return fused_host(layers_host, y_off_host, x, y, Lc, M, ldy, max_NRB, K, max_nch, group_flags, y_f32, 0, stream);
+}
+
+// the same launch with LlamaRMSNorm folded into its staging phase: x is the RAW hidden state [M, K] fp16, norm_w [K] fp16 the norm's
+// weight (XP_RMSNORM).  Every member reads K columns.  PBL_ERR_UNSUPPORTED for column groups and for more rows than one pass takes
+// under the GEMV's LDS budget (route_of's) -- the caller then applies the norm in torch and runs pbl_gemv_f16_fused_host.
+int pbl_gemv_f16_fused_norm_host(const pbl_layer* layers_host, const uint64_t* y_off_host, const void* x, void* y, int Lc, int M,
+                                 uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32,
+                                 const void* norm_w, float norm_eps, void* stream) {
+    if (!layers_host || !y_off_host || !x || !y || !norm_w || Lc < 1 || Lc > PBL_FUSED_INLINE_MAX || M < 1 || !ldy || K < 1)
+        return PBL_ERR_INVALID_ARG;
+    for (int l = 0; l < Lc; ++l)
+        if (layers_host[l].K != K) return PBL_ERR_INVALID_ARG;           // (the weight is read for K columns)
+    if ((group_flags & 1) || M > PBL_MAX_TOKENS_PER_LAUNCH) return PBL_ERR_UNSUPPORTED;
+    return fused_host(layers_host, y_off_host, x, y, Lc, M, ldy, max_NRB, K, max_nch, group_flags, y_f32, 0, stream, norm_w, norm_eps);
 }
 
 // the same launch with bf16 activations converted in the kernel and a bf16 (or fp32) result: see pbl_linear_bf16.  Group-free members
@@ -1447,7 +1608,8 @@ int pbl_gemv_bf16_fused_host(const pbl_layer* layers_host, const uint64_t* y_off
 }
 
 static int fused_host(const pbl_layer* layers_host, const uint64_t* y_off_host, const void* x, void* y, int Lc, int M,
-                      uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32, int x_bf16, void* stream) {
+                      uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32, int x_bf16, void* stream,
+                      const void* norm_w, float norm_eps) {
     if (!layers_host || !y_off_host || !x || !y || Lc < 1 || Lc > PBL_FUSED_INLINE_MAX || M < 1 || M > PBL_MAX_TOKENS_PER_LAUNCH || !ldy)
         return PBL_ERR_INVALID_ARG;
     GemvArgs a{};
@@ -1457,7 +1619,29 @@ static int fused_host(const pbl_layer* layers_host, const uint64_t* y_off_host, 
         a.inl[l] = layers_host[l]; a.inl_off[l] = y_off_host[l];
     }
     a.x_shared = static_cast<const _Float16*>(x); a.y_shared = y; a.ldy = ldy;
+    if (norm_w) {
+        a.norm_w = static_cast<const _Float16*>(norm_w); a.norm_eps = norm_eps;
+        return fused_launch_norm(a, Lc, M, max_NRB, K, max_nch, group_flags, stream);
+    }
     return fused_launch(a, Lc, M, max_NRB, K, max_nch, group_flags, stream);
+}
+
+// fused_launch's group-free route with the RMSNorm prologue, declining what one pass under route_of's LDS budget cannot take
+static int fused_launch_norm(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream) {
+    const uint32_t P = (K + PBL_PANEL_COLS - 1) / PBL_PANEL_COLS;
+    const bool sf = (group_flags & 2) != 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int split = uint64_t(max_NRB) * uint64_t(Lc) >= PBL_SPLIT_TARGET_WAVES ? 1 : pick_split(max_NRB * uint32_t(Lc), P);
+    const int wpb = split > 1 ? split : PBL_GROUPED_WPB;
+    const size_t lds = split > 1 ? lds_bytes(P, max_nch, M, split, split) : lds_bytes(P, max_nch, M, wpb);
+    if (lds > PBL_GEMV_LDS_BUDGET) return PBL_ERR_UNSUPPORTED;
+    const dim3 grid(split > 1 ? max_NRB : (max_NRB + wpb - 1) / wpb, Lc, 1);
+    switch (split) {
+        case 8: return launch_split<8, XP_RMSNORM>(M, sf, a, grid, lds, st);
+        case 4: return launch_split<4, XP_RMSNORM>(M, sf, a, grid, lds, st);
+        case 2: return launch_split<2, XP_RMSNORM>(M, sf, a, grid, lds, st);
+        default: return launch_mb<PBL_GROUPED_WPB, XP_RMSNORM>(M, sf, a, grid, lds, st);
+    }
 }
 
 static int fused_launch(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream) {

@@ -153,6 +153,15 @@ class _FusedMember(nn.Module):
     def forward(self, x):
         g = self._group[0]
         rows = x.numel() // x.shape[-1]
+        if g.norm is not None and g.norm.deferred(x):
+            # folded decode (fuse_decode_(prologues=True)): x is the RAW hidden state its norm passed on unchanged; the launch
+            # normalises it while it stages it
+            if g.x_ref is x and g.x_version == x._version and g.x_normed and self._index in g.pending:
+                g.pending.discard(self._index)
+                g.served += 1
+            else:
+                g.launch(x, rows, self._index, norm=True)
+            return g.outs[self._index].reshape(*x.shape[:-1], self.out_features)
         if not x.is_cuda or (torch.is_grad_enabled() and x.requires_grad):
             return self.own(x)
         fused_ok = rows <= 4 and (x.dtype == torch.float16 or (x.dtype == torch.bfloat16 and g.fused.bf16_ok))
@@ -162,7 +171,7 @@ class _FusedMember(nn.Module):
         merged_ok = not fused_ok and g.merge_batched and 4 < rows <= g.MERGE_MAX_ROWS
         if not (fused_ok or merged_ok):
             return self.own(x)
-        if g.x_ref is x and g.x_version == x._version and self._index in g.pending:     # each launch serves each member once
+        if g.x_ref is x and g.x_version == x._version and not g.x_normed and self._index in g.pending:   # each launch serves each member once
             g.pending.discard(self._index)
             g.served += 1
             return g.outs[self._index].reshape(*x.shape[:-1], self.out_features)
@@ -179,6 +188,8 @@ class _FusedGroup:
     def __init__(self, mods: list[PBLinear], merge_batched: bool = False):
         self.mods = mods
         self.x_ref, self.x_version, self.outs, self.pending = None, -1, None, set()
+        self.x_normed, self.y_all = False, None     # the last launch normalised x (prologue); its whole [rows, sum N] output
+        self.norm = None            # _DeferredNorm whose deferred outputs this group normalises in its launch (prologues=True)
         self.launches = self.served = self.solo_launches = self.merged_launches = 0
         self._warned = False
         self.merged = None          # the members as ONE PBLinear (rows concatenated), built on the first batched call
@@ -214,7 +225,9 @@ class _FusedGroup:
                 self.offs.append(self.offs[-1] + m.out_features)
         return self.merged
 
-    def launch(self, x, rows, index, merged: bool = False):
+    def launch(self, x, rows, index, merged: bool = False, norm: bool = False):
+        """index: the calling member (None: a caller that takes the whole output, _FoldedMLP).  norm: x is the raw hidden state of
+        self.norm -- the launch normalises it (the RMSNorm prologue), or, where the entry declines, the kept norm runs in torch first"""
         if self.pending and self.launches and len(self.pending) == len(self.mods) - 1:
             self.solo_launches += 1          # the previous launch served nobody but its caller
             if self.solo_launches == self.SOLO_WARN_AFTER and not self._warned:
@@ -224,21 +237,136 @@ class _FusedGroup:
                               "not pass one tensor object to its q/k/v (gate/up) projections; fuse_decode_ gains nothing here")
         if self._stamp() != self.stamp:
             self._build()
+        self.y_all = None
         if merged:
             y = self._merged()(x.reshape(rows, x.shape[-1]))
             self.outs = [y[:, self.offs[i]:self.offs[i + 1]] for i in range(len(self.mods))]
             self.merged_launches += 1
         else:
-            self.outs = self.fused(x.reshape(rows, x.shape[-1]).contiguous())
-        self.x_ref, self.x_version = x, x._version
-        self.pending = set(range(len(self.mods))) - {index}
+            x2 = x.reshape(rows, x.shape[-1]).contiguous()
+            y = None
+            if norm:
+                y = self.fused.run(x2, norm=(self.norm.norm.weight, self.norm.eps))
+                if y is None:
+                    x2 = self.norm.norm(x).reshape(rows, x.shape[-1]).contiguous()
+            if y is None:
+                y = self.fused.run(x2)
+            self.y_all = y
+            self.outs = [y[:, int(self.fused.offs[i]):int(self.fused.offs[i + 1])] for i in range(len(self.mods))]
+        self.x_ref, self.x_version, self.x_normed = x, x._version, norm
+        self.pending = set() if index is None else set(range(len(self.mods))) - {index}
         self.launches += 1
 
 
 FUSE_SETS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))     # LLaMA naming (HF)
 
 
-def fuse_decode_(model: nn.Module, sets=FUSE_SETS, merge_batched: bool = False) -> int:
+def _prologue_ok(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """THE predicate of the folded decode path (fuse_decode_(prologues=True)): a deferring norm passes x on unchanged exactly when it
+    holds, and the fused group it feeds evaluates it again on the same tensor -- fp16 on the GPU, at most 4 rows, no autograd"""
+    return (x.is_cuda and x.dtype == torch.float16 and x.dim() >= 1 and 1 <= x.numel() // max(x.shape[-1], 1) <= 4
+            and weight.dtype == torch.float16 and weight.device == x.device
+            and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)))
+
+
+class _DeferredNorm(nn.Module):
+    """Stands where a decoder layer's LlamaRMSNorm stood (fuse_decode_(prologues=True)).  When the folded path takes the call
+    (_prologue_ok) it returns its input UNCHANGED -- the same tensor object -- and the fused launch that reads it (q/k/v, gate/up)
+    normalises it in its staging phase; otherwise it calls the kept norm, bit-identical to the unfolded model."""
+
+    def __init__(self, norm: nn.Module):
+        super().__init__()
+        self.norm = norm                    # registered: state_dict / .to() keep working
+        self.eps = float(norm.variance_epsilon)
+        self.x_ref, self.x_version = None, -1
+
+    @property
+    def weight(self):
+        return self.norm.weight
+
+    @property
+    def variance_epsilon(self):
+        return self.eps
+
+    def forward(self, x):
+        if _prologue_ok(x, self.norm.weight):
+            self.x_ref, self.x_version = x, x._version        # (held until the next call: the identity cannot be a recycled address)
+            return x
+        self.x_ref = None
+        return self.norm(x)
+
+    def deferred(self, x) -> bool:
+        """x is what this norm passed on un-normalised (and the predicate still holds for it)"""
+        return self.x_ref is x and self.x_version == x._version and _prologue_ok(x, self.norm.weight)
+
+
+class _FoldedMLP(nn.Module):
+    """Stands where a LlamaMLP stood (fuse_decode_(prologues=True)); gate_proj / up_proj / down_proj stay its registered children.
+    Fed by its deferred post-attention norm: ONE gate/up launch (RMSNorm prologue) and ONE down_proj launch that builds silu(gate) *
+    up while it stages its input (PBLinear.forward_swiglu).  Otherwise LlamaMLP's arithmetic, unchanged."""
+
+    def __init__(self, mlp: nn.Module, norm: _DeferredNorm):
+        super().__init__()
+        self.config = mlp.config
+        self.hidden_size, self.intermediate_size = mlp.hidden_size, mlp.intermediate_size
+        self.gate_proj, self.up_proj, self.down_proj = mlp.gate_proj, mlp.up_proj, mlp.down_proj
+        self.act_fn = mlp.act_fn
+        self._norm = [norm]                 # (list: the norm is registered at its own place in the layer)
+
+    def forward(self, x):
+        if self._norm[0].deferred(x):
+            grp = self.gate_proj._group[0]
+            rows = x.numel() // x.shape[-1]
+            grp.launch(x, rows, None, norm=True)
+            gu = grp.y_all                                          # [rows, 2 I]: gate at column 0, up at column I
+            inter = self.down_proj.in_features
+            y = self.down_proj.forward_swiglu(gu, inter)
+            if y is None:                                           # declined (rows / LDS budget): the unfused tail
+                y = self.down_proj(self.act_fn(gu[:, :inter]) * gu[:, inter:2 * inter])
+            return y.reshape(*x.shape[:-1], y.shape[-1])
+        return self.down_proj(self.act_fn(self.gate_proj(x)) * self.up_proj(x))
+
+
+def _fold_prologues_(model: nn.Module) -> int:
+    """fuse_decode_(prologues=True): the LLaMA decoder layers whose norms and MLP can be folded into their fused launches"""
+    try:
+        from transformers.models.llama.modeling_llama import LlamaDecoderLayer, LlamaMLP, LlamaRMSNorm
+    except ImportError:
+        return 0
+
+    def group_of(members):
+        if not all(isinstance(m_, _FusedMember) for m_ in members):
+            return None
+        g = members[0]._group[0]
+        ok = all(m_._group[0] is g and m_._index == i for i, m_ in enumerate(members)) and len(g.mods) == len(members)
+        ok = ok and g.norm is None and g.fused._inline and not g.fused.flags & 1
+        return g if ok and all(m_.own.packed.G == 1 and m_.own.weight_dtype == torch.float16 for m_ in members) else None
+
+    n = 0
+    for layer in list(model.modules()):
+        if not isinstance(layer, LlamaDecoderLayer):
+            continue
+        norms = (getattr(layer, "input_layernorm", None), getattr(layer, "post_attention_layernorm", None))
+        if not all(isinstance(nm, LlamaRMSNorm) and nm.weight.dtype == torch.float16 and nm.weight.is_cuda for nm in norms):
+            continue
+        attn, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
+        if not isinstance(mlp, LlamaMLP) or getattr(mlp.config, "hidden_act", None) != "silu" or attn is None:
+            continue
+        g_qkv = group_of([getattr(attn, nm, None) for nm in ("q_proj", "k_proj", "v_proj")])
+        g_gu = group_of([mlp.gate_proj, mlp.up_proj])
+        down = mlp.down_proj
+        if g_qkv is None or g_gu is None or not isinstance(down, PBLinear) or down.packed.G != 1 \
+                or down.weight_dtype != torch.float16 or not down.pbl_blob.is_cuda or down.in_features != mlp.gate_proj.out_features:
+            continue
+        d_in, d_post = _DeferredNorm(norms[0]), _DeferredNorm(norms[1])
+        g_qkv.norm, g_gu.norm = d_in, d_post
+        layer.input_layernorm, layer.post_attention_layernorm = d_in, d_post
+        layer.mlp = _FoldedMLP(mlp, d_post)
+        n += 1
+    return n
+
+
+def fuse_decode_(model: nn.Module, sets=FUSE_SETS, merge_batched: bool = False, prologues: bool = False) -> int:
     """Decode-time fusion: in every module that holds all the projections of a set as PBLinears with one
     in_features (HF LlamaAttention: q/k/v_proj; LlamaMLP: gate/up_proj), replace them by members of one fused launch.
     7 launches per decoder layer become 4.  Returns the number of groups created.  The caller this serves is the token
@@ -247,7 +375,12 @@ def fuse_decode_(model: nn.Module, sets=FUSE_SETS, merge_batched: bool = False) 
     decode BATCH (5 - 64 rows) runs each group as ONE call of the members' row-wise concatenation (packing.concat_rows; built on the
     first such call; costs the members' packed bytes once more plus its GEMM image -- logged once per group at INFO level on the
     "pb_llm_amd" logger) instead of one small-batch launch + reduce per projection (llama-7b decoder layer at 16 rows: 94.0 -> 78.5
-    us).  A decode-only phase at batch <= 4 never reads a GEMM image: `drop_gemm_images_` releases them."""
+    us).  A decode-only phase at batch <= 4 never reads a GEMM image: `drop_gemm_images_` releases them.
+    prologues (OPT-IN): in every HF LlamaDecoderLayer whose norms are fp16 LlamaRMSNorms, whose hidden_act is silu and whose q/k/v,
+    gate/up and down_proj are group-free fp16-exact PBLinears, fold the two RMSNorms into the q/k/v and gate/up launches and
+    silu(gate) * up into the down_proj launch (their staging phases build the row they multiply): at <= 4 fp16 rows 18 small torch
+    kernels per layer disappear and the linears stay 4 launches.  Every other call runs what the unfolded model runs.  The folded
+    layers are counted once at INFO level on the "pb_llm_amd" logger; the return value is the number of groups, as without it."""
     n = 0
     for mod in list(model.modules()):
         for names in sets:
@@ -260,6 +393,11 @@ def fuse_decode_(model: nn.Module, sets=FUSE_SETS, merge_batched: bool = False) 
             for i, (nm, m_) in enumerate(zip(names, subs)):
                 setattr(mod, nm, _FusedMember(grp, i, m_))
             n += 1
+    if prologues:
+        folded = _fold_prologues_(model)
+        import logging
+        logging.getLogger("pb_llm_amd").info("fuse_decode_(prologues=True): RMSNorm and SwiGLU folded into the decode launches of %d "
+                                             "decoder layers", folded)
     return n
 
 

@@ -903,6 +903,27 @@ class PBLinear(nn.Module, BinaryInterface):
         dd = torch.float16 if self.weight_dtype == torch.float16 else torch.float32
         return pb_linear_forward(self.packed, self.pbl_bias, x, dense_dtype=dd)
 
+    def forward_swiglu(self, gate_up: torch.Tensor, inter: int) -> torch.Tensor | None:
+        """self(silu(gate) * up) in ONE launch (pbl_linear_f16_swiglu: the GEMV builds its input row while it stages it) for
+        gate_up [M, >= 2 inter] fp16 with gate at columns [0, inter) and up at [inter, 2 inter) -- the fused gate/up launch's output.
+        Returns [M, out_features] fp16, or None when the entry declines (column groups, more rows than one GEMV pass takes): the
+        caller then runs the unfused composition."""
+        if gate_up.dim() != 2 or gate_up.dtype != torch.float16 or not gate_up.is_cuda or gate_up.stride(-1) != 1 \
+                or inter != self.in_features or gate_up.shape[1] < 2 * inter:
+            raise ValueError("forward_swiglu: gate_up must be an fp16 [M, >= 2 in_features] GPU tensor with unit column stride")
+        if self._image_only is not None or not self.pbl_blob.is_cuda or self.pbl_blob.device != gate_up.device:
+            return None
+        M = gate_up.shape[0]
+        ldx = gate_up.stride(0) if M > 1 else gate_up.shape[1]
+        layer = self.packed.layer_struct(self.pbl_bias)
+        y = torch.empty(M, self.out_features, dtype=torch.float16, device=gate_up.device)
+        rc = _lib.lib().pbl_linear_f16_swiglu(C.byref(layer), gate_up.data_ptr(), ldx, inter, y.data_ptr(), M, 0,
+                                              torch.cuda.current_stream(gate_up.device).cuda_stream)
+        if rc == _lib.PBL_ERR_UNSUPPORTED:
+            return None
+        _lib.check(rc, "linear (SwiGLU prologue)")
+        return y
+
     def to_regular_linear(self) -> nn.Linear:
         lin = nn.Linear(self.in_features, self.out_features, bias=self.pbl_bias is not None)
         w = self.weight

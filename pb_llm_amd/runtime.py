@@ -99,14 +99,39 @@ class FusedGemv:
         self.flags = int(any(p.G > 1 for p in self.packed)) | 2 * int(any(p.flags & _lib.PBL_FLAG_SAL_F16 for p in self.packed))
         self.bf16_ok = self._inline and not (self.flags & 1)
 
-    def __call__(self, x2: torch.Tensor, out_f32: bool = False) -> list[torch.Tensor]:
+    def __call__(self, x2: torch.Tensor, out_f32: bool = False, norm=None) -> list[torch.Tensor] | None:
+        """norm=(weight, eps): x2 is the RAW hidden state and the launch multiplies LlamaRMSNorm(x2) (weight [K] fp16, the norm's
+        variance_epsilon) -- the normalisation runs in the kernel's staging phase (pbl_gemv_f16_fused_norm_host).  None when that
+        entry declines (column groups, more rows than one pass takes): the caller applies the norm itself and calls again."""
+        y = self.run(x2, out_f32, norm)
+        if y is None:
+            return None
+        return [y[:, int(self.offs[i]):int(self.offs[i + 1])] for i in range(len(self.packed))]
+
+    def run(self, x2: torch.Tensor, out_f32: bool = False, norm=None) -> torch.Tensor | None:
+        """the launch behind __call__: the whole [M, sum N_l] output (member l at columns offs[l] .. offs[l + 1])"""
         M = x2.shape[0]
         if x2.dtype not in (torch.float16, torch.bfloat16) or not x2.is_contiguous() or x2.shape[1] != self.K or not 1 <= M <= _lib.PBL_MAX_TOKENS_PER_LAUNCH:
             raise _lib.PblError("FusedGemv: x must be a contiguous fp16 / bf16 [M <= 4, K] tensor")
         total = int(self.offs[-1])
+        L = _lib.lib()
+        if norm is not None:
+            w, eps = norm
+            if x2.dtype != torch.float16 or w.dtype != torch.float16 or w.device != x2.device or not w.is_contiguous() or w.numel() != self.K:
+                raise _lib.PblError("FusedGemv: the RMSNorm prologue takes fp16 x and an fp16 [K] weight on x's device")
+            if not self._inline:
+                return None
+            y = torch.empty(M, total, dtype=torch.float32 if out_f32 else x2.dtype, device=x2.device)
+            st = torch.cuda.current_stream(x2.device).cuda_stream
+            rc = L.pbl_gemv_f16_fused_norm_host(C.addressof(self._structs_host), C.addressof(self._yoff_host), x2.data_ptr(), y.data_ptr(),
+                                                len(self.packed), M, total, self.max_NRB, self.K, self.max_nch, self.flags,
+                                                int(out_f32), w.data_ptr(), float(eps), st)
+            if rc == _lib.PBL_ERR_UNSUPPORTED:
+                return None
+            _lib.check(rc, "fused gemv (RMSNorm prologue)")
+            return y
         y = torch.empty(M, total, dtype=torch.float32 if out_f32 else x2.dtype, device=x2.device)
         st = torch.cuda.current_stream(x2.device).cuda_stream
-        L = _lib.lib()
         if x2.dtype == torch.bfloat16:
             # bf16 activations converted IN the launch, bf16 result (pbl_gemv_bf16_fused_host; group-free members, at most
             # PBL_FUSED_INLINE_MAX of them: what q/k/v and gate/up are)
@@ -123,7 +148,7 @@ class FusedGemv:
             _lib.check(L.pbl_gemv_f16_fused(self._layers_dev.data_ptr(), self._yoff_dev.data_ptr(), x2.data_ptr(), y.data_ptr(),
                                             len(self.packed), M, total, self.max_NRB, self.K, self.max_nch, self.flags,
                                             int(out_f32), st), "fused gemv")
-        return [y[:, int(self.offs[i]):int(self.offs[i + 1])] for i in range(len(self.packed))]
+        return y
 
     def algorithmic_bytes(self, M: int = 1) -> int:
         # x is read once for the group, not once per layer
