@@ -490,6 +490,27 @@ int pbl_gemv_f16_fused_norm_host(const pbl_layer* layers_host, const uint64_t* y
 int pbl_linear_f16_swiglu(const pbl_layer* layer, const void* gate_up, uint32_t ldx, uint32_t up_off, void* y, int M, int y_f32,
                           void* stream);
 
+/* Decode epilogues of a LLaMA decoder layer (same one-pass, group-free scope as the prologues above; fp16 results only).
+ *   pbl_linear_f16_residual        y [M, N] = fp16(fp16(layer(x)) + residual): x [M, K] fp16, residual [M, ldr] fp16 (ldr >= N) --
+ *                                  HF's `residual + o_proj(attn)`: the linear's fp16 output, then the fp16 add (fp32 opmath, one
+ *                                  rounding); overflow gives +-inf, NaN propagates.
+ *   pbl_linear_f16_swiglu_residual pbl_linear_f16_swiglu's prologue and the same epilogue: `h1 + down_proj(silu(gate) * up)`.
+ *   pbl_rope_f16                   HF's apply_rotary_pos_emb on the q and k heads of a fused q/k/v output qkv [B S, ld] fp16 (token
+ *                                  b S + s; Hq q heads from column q_off, Hkv k heads from k_off, head_dim D): q_out / k_out [B, H, S,
+ *                                  D] fp16 with element strides {b, h, s} (q_ostride / k_ostride, host arrays of 3) and unit d stride
+ *                                  = fp16(fp16(x * cos) + fp16(rotate_half(x) * sin)), the roundings of torch's three kernels.  The
+ *                                  cos / sin row of token (b, s) starts at b cos_sb + s cos_ss elements (0 broadcasts one row);
+ *                                  cos_dim is their last dimension.  PBL_ERR_UNSUPPORTED: odd D, D > 256, cos_dim != D.
+ * All three: PBL_ERR_INVALID_ARG for NULL pointers, inconsistent sizes and an output that overlaps an input, before any device work;
+ * the two linears answer PBL_ERR_UNSUPPORTED where pbl_linear_f16_swiglu does (the caller runs the unfused composition).  None of
+ * them synchronises or allocates: all can be captured in a hipGraph. */
+int pbl_linear_f16_residual(const pbl_layer* layer, const void* x, const void* residual, uint32_t ldr, void* y, int M, void* stream);
+int pbl_linear_f16_swiglu_residual(const pbl_layer* layer, const void* gate_up, uint32_t ldx, uint32_t up_off, const void* residual,
+                                   uint32_t ldr, void* y, int M, void* stream);
+int pbl_rope_f16(const void* qkv, uint32_t ld, uint32_t q_off, uint32_t k_off, int B, int S, int Hq, int Hkv, int D,
+                 const void* cos, const void* sin, int cos_dim, int64_t cos_sb, int64_t cos_ss,
+                 void* q_out, const int64_t* q_ostride, void* k_out, const int64_t* k_ostride, void* stream);
+
 /* ---------------- QAT step, weight side ------------------------------------------ */
 /* The elementwise work of one training step of BinaryXnorExceptOutliersLinear
  * (quant/outlier_quantizer.py:83-99; straight-through estimator quant/quantizer.py:18-25), fused into

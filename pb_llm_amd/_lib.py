@@ -59,7 +59,8 @@ EXPORTS = ["pbl_status_string", "pbl_version", "pbl_pack_dense_f32", "pbl_pack_d
            "pbl_linear_f16_push", "pbl_p2p_reduce_f32_dev", "pbl_linear_push_max_tokens",
            "pbl_gemm_f16_image_ex", "pbl_act_bf16_prepare", "pbl_act_finish",
            "pbl_linear_bf16", "pbl_gemv_bf16_fused_host", "pbl_gemm_image_workspace_bytes", "pbl_gemm_image_plan",
-           "pbl_gemm_f16_image_ws", "pbl_gemv_f16_fused_norm_host", "pbl_linear_f16_swiglu"]
+           "pbl_gemm_f16_image_ws", "pbl_gemv_f16_fused_norm_host", "pbl_linear_f16_swiglu",
+           "pbl_linear_f16_residual", "pbl_linear_f16_swiglu_residual", "pbl_rope_f16"]
 
 
 def lib() -> C.CDLL:
@@ -219,6 +220,13 @@ def lib() -> C.CDLL:
     L.pbl_gemv_f16_fused_norm_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, u32, u32, u32, u32, C.c_int, C.c_int, vp, C.c_float, vp]
     L.pbl_linear_f16_swiglu.restype = C.c_int
     L.pbl_linear_f16_swiglu.argtypes = [C.POINTER(PblLayer), vp, u32, u32, vp, C.c_int, C.c_int, vp]
+    L.pbl_linear_f16_residual.restype = C.c_int
+    L.pbl_linear_f16_residual.argtypes = [C.POINTER(PblLayer), vp, vp, u32, vp, C.c_int, vp]
+    L.pbl_linear_f16_swiglu_residual.restype = C.c_int
+    L.pbl_linear_f16_swiglu_residual.argtypes = [C.POINTER(PblLayer), vp, u32, u32, vp, u32, vp, C.c_int, vp]
+    L.pbl_rope_f16.restype = C.c_int
+    L.pbl_rope_f16.argtypes = [vp, u32, u32, u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64, C.c_int64,
+                               vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp]
     _lib = L
     return L
 

@@ -236,8 +236,13 @@ struct GemvArgs {
     float norm_eps;
     uint32_t ldx;
     uint32_t up_off;
+    // residual epilogue (XE_RESIDUAL; pbl_linear_f16_residual / pbl_linear_f16_swiglu_residual): y[m, n] = fp16(fp16(linear) +
+    // residual[m * ldr + n]) -- HF's `residual + hidden_states` after the linear's own fp16 result.  (At the END of the struct.)
+    const _Float16* residual;
+    uint32_t ldr;
 };
-enum { XP_NONE = 0, XP_RMSNORM = 1, XP_SWIGLU = 2 };
+// XP: the x prologue in bits 0..1, the residual epilogue as bit 2 (a flag, so that XP_NONE -- the headline kernel -- keeps its name)
+enum { XP_NONE = 0, XP_RMSNORM = 1, XP_SWIGLU = 2, XE_RESIDUAL = 4 };
 
 // Gather 8 fp16 values from LDS byte addresses a[0..7] into 4 packed half2 registers
 // (entry 2p in the low half, 2p+1 in the high half).  All loads are in flight and waited
@@ -361,14 +366,15 @@ __device__ __forceinline__ uint32_t rmsnorm_f16(uint32_t xb, uint32_t gb, float 
 // XB: bf16 activations converted in the staging phase, bf16 result (GemvArgs.x_bf16).  A template parameter, not a run-time branch:
 // the fp16 instantiations -- the headline kernel among them -- are the code they were.  XP (x prologue, fp16 only): XP_RMSNORM stages
 // LlamaRMSNorm(x) (pass 1: every token's sum of squares, one barrier, pass 2: the normalised row), XP_SWIGLU stages silu(gate) * up.
+// XE_RESIDUAL (or-ed in) adds the residual in the store: fp16 result, then the fp16 add.
 template <int MB, int WPB, bool SF, int SPLIT, bool XB = false, int XP = XP_NONE>
 __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void pbl_gemv_kernel(GemvArgs args) {
     static_assert(SPLIT == 1 || SPLIT == WPB, "split mode uses every wave of the workgroup on one record");
-    static_assert(!(XB && XP != XP_NONE), "the x prologues take fp16 activations");
+    static_assert(!(XB && XP != XP_NONE), "the x prologues and the residual epilogue take fp16 activations");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ uint32_t s_amax[XB ? MB * WPB : 1];           // XB: per (token, wave) the largest |x| bit pattern
     __shared__ float s_tscale[XB ? MB : 1];                  //     per token the power of two (or +inf) the result is multiplied with
-    __shared__ float s_ssq[XP == XP_RMSNORM ? MB * WPB : 1]; // XP_RMSNORM: per (token, wave) the partial sum of squares
+    __shared__ float s_ssq[(XP & 3) == XP_RMSNORM ? MB * WPB : 1]; // XP_RMSNORM: per (token, wave) the partial sum of squares
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -520,7 +526,7 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
             }
             for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
         }
-    } else if constexpr (XP == XP_RMSNORM) {
+    } else if constexpr ((XP & 3) == XP_RMSNORM) {
         // LlamaRMSNorm.forward on an fp16 row: pass 1 sums x^2 in fp32 (x^2 of an fp16 value is exact), one partial per (token, wave),
         // one barrier; pass 2 re-reads the row and the weight (L1 / L2) and writes fp16(g * fp16(x * r)), r = 1 / sqrt(mean + eps)
         // with an IEEE sqrt and divide.  mean = sum * (1 / K) as torch's mean kernel scales.  inf / NaN in a row: r = 0 or NaN, as HF.
@@ -577,7 +583,7 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
             }
             for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
         }
-    } else if constexpr (XP == XP_SWIGLU) {
+    } else if constexpr ((XP & 3) == XP_SWIGLU) {
         // silu(gate) * up from the fused gate/up launch's output: row m holds gate at [0, K) and up at [up_off, up_off + K)
         const int nthr = WPB * PBL_WAVE;
         const uint16_t* xb = reinterpret_cast<const uint16_t*>(xg);
@@ -805,7 +811,11 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
                     pblp2p::slot_ptr(args.push_peer[p], push_set, args.push_rank, args.push_world, args.push_cap)[size_t(m) * ldy + row] = yv;
             } else if (args.y_f32) static_cast<float*>(yg)[size_t(m) * ldy + row] = yv;
             else if constexpr (XB) static_cast<uint16_t*>(yg)[size_t(m) * ldy + row] = uint16_t(bf16_bits_rne(yv));
-            else static_cast<_Float16*>(yg)[size_t(m) * ldy + row] = _Float16(yv);
+            else if constexpr ((XP & XE_RESIDUAL) != 0) {
+                // two roundings, as HF: the linear's fp16 output, then the fp16 add (fp32 opmath); +-inf / NaN propagate
+                const _Float16 lin = _Float16(yv);
+                static_cast<_Float16*>(yg)[size_t(m) * ldy + row] = _Float16(float(lin) + float(args.residual[size_t(m) * args.ldr + row]));
+            } else static_cast<_Float16*>(yg)[size_t(m) * ldy + row] = _Float16(yv);
         }
     }
     if (args.push_world) {
@@ -835,13 +845,13 @@ size_t lds_bytes(uint32_t P, uint32_t max_nch, int mb, int wpb, int split = 1) {
 template <int MB, int WPB, bool SF, int SPLIT = 1, int XP = XP_NONE>
 int launch(const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
     void (*k)(GemvArgs);
-    if constexpr (XP != XP_NONE) k = pbl_gemv_kernel<MB, WPB, SF, SPLIT, false, XP>;     // (x prologues: fp16 only)
+    if constexpr (XP != XP_NONE) k = pbl_gemv_kernel<MB, WPB, SF, SPLIT, false, XP>;     // (prologues / epilogue: fp16 only)
     else k = a.x_bf16 ? pbl_gemv_kernel<MB, WPB, SF, SPLIT, true> : pbl_gemv_kernel<MB, WPB, SF, SPLIT, false>;
     // the bf16 instantiation holds s_amax / s_tscale in STATIC LDS on top of the dynamic size (4 MB (WPB + 1) bytes, rounded up):
     // both limits are on the sum (a layer just under a limit failed the launch instead of answering UNSUPPORTED, which
     // pbl_linear_bf16's callers turn into the three-launch form); the RMSNorm prologue holds s_ssq (4 MB WPB bytes) the same way
     const size_t stat = a.x_bf16 ? ((size_t(4) * MB * (WPB + 1) + 15) & ~size_t(15)) + 16
-                      : XP == XP_RMSNORM ? ((size_t(4) * MB * WPB + 15) & ~size_t(15)) + 16 : 16;
+                      : (XP & 3) == XP_RMSNORM ? ((size_t(4) * MB * WPB + 15) & ~size_t(15)) + 16 : 16;
     const bool declines = a.x_bf16 || XP != XP_NONE;             // callers that have an unfused form to fall back to
     if (lds + stat > 64 * 1024) {
         if (lds + stat > 160 * 1024) return PBL_ERR_UNSUPPORTED;
@@ -1288,6 +1298,78 @@ int pick_split(uint32_t records, uint32_t P) {
     return s;
 }
 
+// [a, a + na) and [b, b + nb) share a byte
+bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return na && nb && x < y + nb && y < x + na;
+}
+
+// one GEMV pass of a group-free layer with a prologue / epilogue instantiation, on route_of's split / wpb (the caller has checked
+// M against its one-pass limit)
+template <int XP>
+int one_pass(const pbl_layer* layer, int split, int wpb, GemvArgs& a, int M, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool sf = layer->flags & PBL_FLAG_SAL_F16;
+    const dim3 grid(split > 1 ? layer->NRB : (layer->NRB + wpb - 1) / wpb, 1, 1);
+    const size_t lds = lds_bytes(layer->P, layer->max_nch, M, wpb, split);
+    switch (split) {
+        case 8: return launch_split<8, XP>(M, sf, a, grid, lds, st);
+        case 4: return launch_split<4, XP>(M, sf, a, grid, lds, st);
+        case 2: return launch_split<2, XP>(M, sf, a, grid, lds, st);
+        default: return wpb == 4 ? launch_mb<4, XP>(M, sf, a, grid, lds, st) : launch_mb<1, XP>(M, sf, a, grid, lds, st);
+    }
+}
+
+// ---- rotary position embedding of a decode step (pbl_rope_f16) -----------------------------------------------------------------
+struct RopeArgs {
+    const uint16_t* qkv;            // [M, ld] fp16: q heads at column q_off, k heads at k_off (token m = b * S + s)
+    const uint16_t* cos;            // cos / sin [.., D] fp16: the row of token (b, s) at b * c_sb + s * c_ss (0: broadcast)
+    const uint16_t* sin;
+    uint16_t* q_out;                // element (b, h, s, d) at b * ob + h * oh + s * os + d
+    uint16_t* k_out;
+    int64_t c_sb, c_ss;
+    int64_t q_ob, q_oh, q_os, k_ob, k_oh, k_os;
+    uint32_t ld, q_off, k_off;
+    int S, Hq, H, half, pairs;      // H = Hq + Hkv; pairs = M * H * half
+};
+
+// a value the compiler cannot trace back to an fp16 operand: the arithmetic on it stays fp32 (no fp16 / mixed-precision rewrite)
+__device__ __forceinline__ float opaque(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+// (a * b) rounded to fp16, as torch's `*` on half tensors: an fp32 product (exact for two fp16 values), one rounding.  The product
+// is materialised before the rounding: fptrunc(fmul) would otherwise become v_fma_mixlo_f16 with a +0 addend, which turns a -0
+// product into +0.
+__device__ __forceinline__ float mul_f16(float a, float b) {
+#pragma clang fp contract(off)
+    return opaque(float(_Float16(opaque(opaque(a) * opaque(b)))));
+}
+
+// HF's apply_rotary_pos_emb on half tensors, one (d, d + D/2) pair per thread: q * cos and rotate_half(q) * sin each rounded to
+// fp16, then their sum rounded to fp16 -- the three torch kernels' roundings, never contracted into an fma.  inf / NaN propagate.
+__global__ __launch_bounds__(256) void pbl_rope_kernel(RopeArgs a) {
+#pragma clang fp contract(off)
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= a.pairs) return;
+    const int i = idx % a.half, t = idx / a.half;
+    const int h = t % a.H, m = t / a.H;
+    const int b = m / a.S, s = m - b * a.S;
+    const bool isq = h < a.Hq;
+    const int hh = isq ? h : h - a.Hq;
+    const int D = 2 * a.half;
+    const uint16_t* x = a.qkv + size_t(m) * a.ld + (isq ? a.q_off : a.k_off) + size_t(hh) * D;
+    const int64_t crow = b * a.c_sb + s * a.c_ss;
+    const float x1 = float(__builtin_bit_cast(_Float16, x[i])), x2 = float(__builtin_bit_cast(_Float16, x[i + a.half]));
+    const float c1 = float(__builtin_bit_cast(_Float16, a.cos[crow + i])), c2 = float(__builtin_bit_cast(_Float16, a.cos[crow + i + a.half]));
+    const float s1 = float(__builtin_bit_cast(_Float16, a.sin[crow + i])), s2 = float(__builtin_bit_cast(_Float16, a.sin[crow + i + a.half]));
+    const _Float16 o1 = _Float16(mul_f16(x1, c1) + mul_f16(-x2, s1));      // rotate_half: (-x2, x1); fp32 sum, one rounding
+    const _Float16 o2 = _Float16(mul_f16(x2, c2) + mul_f16(x1, s2));
+    uint16_t* out = isq ? a.q_out + (b * a.q_ob + hh * a.q_oh + s * a.q_os) : a.k_out + (b * a.k_ob + hh * a.k_oh + s * a.k_os);
+    out[i] = __builtin_bit_cast(uint16_t, o1);
+    out[i + a.half] = __builtin_bit_cast(uint16_t, o2);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1465,6 +1547,95 @@ int pbl_linear_f16_swiglu(const pbl_layer* layer, const void* gate_up, uint32_t 
         case 2: return launch_split<2, XP_SWIGLU>(M, sf, a, grid, lds, st);
         default: return wpb == 4 ? launch_mb<4, XP_SWIGLU>(M, sf, a, grid, lds, st) : launch_mb<1, XP_SWIGLU>(M, sf, a, grid, lds, st);
     }
+}
+
+// A decoder layer's residual adds in the GEMV's store (XE_RESIDUAL): y [M, N] fp16 = fp16(fp16(layer(x)) + residual), residual
+// [M, ldr] fp16 -- HF's `residual + o_proj(attn)` in ONE launch.  One GEMV pass of a group-free layer (as pbl_linear_f16_swiglu):
+// PBL_ERR_UNSUPPORTED otherwise -- the caller runs the layer and the add.  y must not overlap x or the residual.
+int pbl_linear_f16_residual(const pbl_layer* layer, const void* x, const void* residual, uint32_t ldr, void* y, int M, void* stream) {
+    if (!layer || !layer->blob || !x || !residual || !y || M < 1 || M > (1 << 20) || ldr < layer->N) return PBL_ERR_INVALID_ARG;
+    const size_t ybytes = size_t(M) * layer->N * 2;
+    if (overlaps(y, ybytes, x, size_t(M) * layer->K * 2) || overlaps(y, ybytes, residual, (size_t(M - 1) * ldr + layer->N) * 2))
+        return PBL_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
+    if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
+    const Route r = route_of(layer, M, true);
+    if (M > r.mb_max) return PBL_ERR_UNSUPPORTED;
+    GemvArgs a{};
+    a.layer = *layer;
+    a.x = static_cast<const _Float16*>(x);
+    a.y = y;
+    a.M = M; a.y_f32 = 0; a.grouped = 0;
+    a.residual = static_cast<const _Float16*>(residual); a.ldr = ldr;
+    return one_pass<XP_NONE | XE_RESIDUAL>(layer, r.split, r.wpb, a, M, stream);
+}
+
+// LLaMA's whole MLP tail in ONE launch: y [M, N] fp16 = fp16(fp16(layer(silu(gate) * up)) + residual) -- pbl_linear_f16_swiglu's
+// prologue and pbl_linear_f16_residual's epilogue.  Same declines; y must not overlap gate_up or the residual.
+int pbl_linear_f16_swiglu_residual(const pbl_layer* layer, const void* gate_up, uint32_t ldx, uint32_t up_off, const void* residual,
+                                   uint32_t ldr, void* y, int M, void* stream) {
+    if (!layer || !layer->blob || !gate_up || !residual || !y || M < 1 || M > (1 << 20) || up_off < layer->K ||
+        uint64_t(ldx) < uint64_t(up_off) + layer->K || ldr < layer->N)
+        return PBL_ERR_INVALID_ARG;
+    const size_t ybytes = size_t(M) * layer->N * 2;
+    if (overlaps(y, ybytes, gate_up, (size_t(M - 1) * ldx + up_off + layer->K) * 2) ||
+        overlaps(y, ybytes, residual, (size_t(M - 1) * ldr + layer->N) * 2))
+        return PBL_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
+    if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
+    const Route r = route_of(layer, M, true);
+    if (M > r.mb_max) return PBL_ERR_UNSUPPORTED;
+    GemvArgs a{};
+    a.layer = *layer;
+    a.x = static_cast<const _Float16*>(gate_up);
+    a.y = y;
+    a.M = M; a.y_f32 = 0; a.grouped = 0;
+    a.ldx = ldx; a.up_off = up_off;
+    a.residual = static_cast<const _Float16*>(residual); a.ldr = ldr;
+    return one_pass<XP_SWIGLU | XE_RESIDUAL>(layer, r.split, r.wpb, a, M, stream);
+}
+
+// HF's apply_rotary_pos_emb for the q and k heads of a fused q/k/v output, in ONE launch (pbl_rope_kernel).  Token m = b * S + s
+// of qkv [B S, ld] fp16 holds Hq q heads from column q_off and Hkv k heads from column k_off, head_dim D each.  cos / sin: the row
+// of token (b, s) starts at b * cos_sb + s * cos_ss elements (a stride of 0 broadcasts), cos_dim its length.  q_out / k_out
+// [B, H, S, D] fp16 with element strides {b, h, s} in q_ostride / k_ostride (host arrays) and unit d stride: the layout torch's
+// elementwise kernels give the result.  PBL_ERR_INVALID_ARG (before any device work): NULL pointers, sizes < 1, negative strides,
+// heads outside a row of qkv, an output overlapping an input or the other output.  PBL_ERR_UNSUPPORTED: odd D, D > 256,
+// cos_dim != D.  No allocation, no synchronisation: capturable in a hipGraph.
+int pbl_rope_f16(const void* qkv, uint32_t ld, uint32_t q_off, uint32_t k_off, int B, int S, int Hq, int Hkv, int D,
+                 const void* cos, const void* sin, int cos_dim, int64_t cos_sb, int64_t cos_ss,
+                 void* q_out, const int64_t* q_ostride, void* k_out, const int64_t* k_ostride, void* stream) {
+    if (!qkv || !cos || !sin || !q_out || !k_out || !q_ostride || !k_ostride || B < 1 || S < 1 || Hq < 1 || Hkv < 1 || D < 1 ||
+        cos_dim < 1 || cos_sb < 0 || cos_ss < 0)
+        return PBL_ERR_INVALID_ARG;
+    for (int j = 0; j < 3; ++j)
+        if (q_ostride[j] < 0 || k_ostride[j] < 0) return PBL_ERR_INVALID_ARG;
+    const int64_t M = int64_t(B) * S;
+    const int64_t qend = int64_t(q_off) + int64_t(Hq) * D, kend = int64_t(k_off) + int64_t(Hkv) * D;
+    if (qend > ld || kend > ld || M * (Hq + Hkv) * D > (int64_t(1) << 30)) return PBL_ERR_INVALID_ARG;
+    auto out_bytes = [&](const int64_t* o, int H) {
+        return size_t(((B - 1) * o[0] + int64_t(H - 1) * o[1] + (S - 1) * o[2] + D) * 2);
+    };
+    const size_t qb = out_bytes(q_ostride, Hq), kb = out_bytes(k_ostride, Hkv);
+    const size_t xb = size_t(((M - 1) * ld + (qend > kend ? qend : kend)) * 2);
+    const size_t cb = size_t(((B - 1) * cos_sb + (S - 1) * cos_ss + cos_dim) * 2);
+    if (overlaps(q_out, qb, k_out, kb) || overlaps(q_out, qb, qkv, xb) || overlaps(k_out, kb, qkv, xb) ||
+        overlaps(q_out, qb, cos, cb) || overlaps(k_out, kb, cos, cb) || overlaps(q_out, qb, sin, cb) || overlaps(k_out, kb, sin, cb))
+        return PBL_ERR_INVALID_ARG;
+    if ((D & 1) || D > 256 || cos_dim != D) return PBL_ERR_UNSUPPORTED;
+    RopeArgs a{};
+    a.qkv = static_cast<const uint16_t*>(qkv);
+    a.cos = static_cast<const uint16_t*>(cos); a.sin = static_cast<const uint16_t*>(sin);
+    a.q_out = static_cast<uint16_t*>(q_out); a.k_out = static_cast<uint16_t*>(k_out);
+    a.c_sb = cos_sb; a.c_ss = cos_ss;
+    a.q_ob = q_ostride[0]; a.q_oh = q_ostride[1]; a.q_os = q_ostride[2];
+    a.k_ob = k_ostride[0]; a.k_oh = k_ostride[1]; a.k_os = k_ostride[2];
+    a.ld = ld; a.q_off = q_off; a.k_off = k_off;
+    a.S = S; a.Hq = Hq; a.H = Hq + Hkv; a.half = D / 2;
+    a.pairs = int(M * (Hq + Hkv) * (D / 2));
+    void* argv[] = {&a};
+    return hipLaunchKernel(reinterpret_cast<const void*>(pbl_rope_kernel), dim3((a.pairs + 255) / 256), dim3(256), argv, 0,
+                           static_cast<hipStream_t>(stream)) == hipSuccess ? PBL_OK : PBL_ERR_LAUNCH;
 }
 
 // K-split tensor parallelism, fused: the GEMV of this rank's column shard with its epilogue pushing the fp32 partial y[M, N]

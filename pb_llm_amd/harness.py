@@ -257,6 +257,20 @@ class _FusedGroup:
         self.pending = set() if index is None else set(range(len(self.mods))) - {index}
         self.launches += 1
 
+    def run_folded(self, x, rows, norm: "_DeferredNorm") -> torch.Tensor:
+        """The whole [rows, sum N] output of ONE launch on LlamaRMSNorm(x), for a folded decoder layer (fuse_decode_(epilogues=True)):
+        the RMSNorm prologue, or, where it declines, the kept norm in torch and the plain launch -- what launch(norm=True) runs.  No
+        identity or version bookkeeping (inference tensors have no version counter): no member picks a slice of it up."""
+        if self._stamp() != self.stamp:
+            self._build()
+        x2 = x.reshape(rows, x.shape[-1]).contiguous()
+        y = self.fused.run(x2, norm=(norm.norm.weight, norm.eps))
+        if y is None:
+            y = self.fused.run(norm.norm(x).reshape(rows, x.shape[-1]).contiguous())
+        self.x_ref, self.outs, self.y_all, self.pending = None, None, None, set()
+        self.launches += 1
+        return y
+
 
 FUSE_SETS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))     # LLaMA naming (HF)
 
@@ -327,12 +341,64 @@ class _FoldedMLP(nn.Module):
         return self.down_proj(self.act_fn(self.gate_proj(x)) * self.up_proj(x))
 
 
-def _fold_prologues_(model: nn.Module) -> int:
-    """fuse_decode_(prologues=True): the LLaMA decoder layers whose norms and MLP can be folded into their fused launches"""
+def _folded_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
+                          position_embeddings=None, **kwargs):
+    """LlamaDecoderLayer.forward of a layer folded by fuse_decode_(epilogues=True), installed on the instance.  At <= 4 fp16 rows
+    without autograd, with position_embeddings given: the q/k/v launch (RMSNorm prologue), ONE RoPE launch (runtime.rope_f16),
+    HF's cache update and attention interface, o_proj with the residual add in its store, the gate/up launch (RMSNorm prologue) and
+    down_proj with the SwiGLU prologue and the residual add -- every step with HF's roundings, so the result equals the
+    prologues=True layer's bit for bit.  Every other call runs LlamaDecoderLayer.forward (the prologues=True layer)."""
+    d_in = self.input_layernorm
+    if position_embeddings is None or hidden_states.dim() != 3 or not _prologue_ok(hidden_states, d_in.norm.weight):
+        return type(self).forward(self, hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                  past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings, **kwargs)
+    from transformers.models.llama import modeling_llama as ML
+    from .runtime import rope_f16
+    attn, mlp = self.self_attn, self.mlp
+    B, S, _ = hidden_states.shape
+    rows, D = B * S, attn.head_dim
+    g_qkv = attn.q_proj._group[0]
+    y = g_qkv.run_folded(hidden_states, rows, d_in)
+    o_q, o_k, o_v, o_end = (int(o) for o in g_qkv.fused.offs)
+
+    def heads(a, b):                                       # the view LlamaAttention makes of a projection's output
+        return y[:, a:b].reshape(B, S, b - a).view(B, S, -1, D).transpose(1, 2)
+
+    cos, sin = position_embeddings
+    qk = rope_f16(y, o_q, o_k, B, S, (o_k - o_q) // D, (o_v - o_k) // D, D, cos, sin)
+    if qk is None:
+        qk = ML.apply_rotary_pos_emb(heads(o_q, o_k), heads(o_k, o_v), cos, sin)
+    q, k = qk
+    v = heads(o_v, o_end)
+    if past_key_values is not None:
+        k, v = past_key_values.update(k, v, attn.layer_idx)
+    interface = ML.ALL_ATTENTION_FUNCTIONS.get_interface(attn.config._attn_implementation, ML.eager_attention_forward)
+    a, _ = interface(attn, q, k, v, attention_mask, dropout=0.0 if not attn.training else attn.attention_dropout,
+                     scaling=attn.scaling, position_ids=position_ids, use_cache=use_cache, **kwargs)
+    a = a.reshape(B, S, -1).contiguous()
+    h1 = attn.o_proj.forward_residual(a, hidden_states)
+    if h1 is None:
+        h1 = hidden_states + attn.o_proj(a)
+    gu = mlp.gate_proj._group[0].run_folded(h1, rows, self.post_attention_layernorm)
+    inter = mlp.down_proj.in_features
+    out = mlp.down_proj.forward_swiglu(gu, inter, residual=h1)
+    if out is None:
+        t = mlp.down_proj.forward_swiglu(gu, inter)
+        if t is None:
+            t = mlp.down_proj(mlp.act_fn(gu[:, :inter]) * gu[:, inter:2 * inter])
+        out = h1 + t.reshape(h1.shape)
+    return out.view(h1.shape)
+
+
+def _fold_prologues_(model: nn.Module, epilogues: bool = False) -> tuple[int, int]:
+    """fuse_decode_(prologues=True): the LLaMA decoder layers whose norms and MLP can be folded into their fused launches.
+    epilogues: of those, the layers of type LlamaDecoderLayer with a LlamaAttention and a group-free fp16-exact PBLinear o_proj also
+    get the folded forward (_folded_layer_forward).  Returns (layers folded, layers with the folded forward)."""
     try:
-        from transformers.models.llama.modeling_llama import LlamaDecoderLayer, LlamaMLP, LlamaRMSNorm
+        from transformers.models.llama.modeling_llama import LlamaAttention, LlamaDecoderLayer, LlamaMLP, LlamaRMSNorm
     except ImportError:
-        return 0
+        return 0, 0
+    import types
 
     def group_of(members):
         if not all(isinstance(m_, _FusedMember) for m_ in members):
@@ -342,7 +408,7 @@ def _fold_prologues_(model: nn.Module) -> int:
         ok = ok and g.norm is None and g.fused._inline and not g.fused.flags & 1
         return g if ok and all(m_.own.packed.G == 1 and m_.own.weight_dtype == torch.float16 for m_ in members) else None
 
-    n = 0
+    n = ne = 0
     for layer in list(model.modules()):
         if not isinstance(layer, LlamaDecoderLayer):
             continue
@@ -363,10 +429,15 @@ def _fold_prologues_(model: nn.Module) -> int:
         layer.input_layernorm, layer.post_attention_layernorm = d_in, d_post
         layer.mlp = _FoldedMLP(mlp, d_post)
         n += 1
-    return n
+        o = getattr(attn, "o_proj", None)
+        if epilogues and type(layer) is LlamaDecoderLayer and type(attn) is LlamaAttention and isinstance(o, PBLinear) \
+                and o.packed.G == 1 and o.weight_dtype == torch.float16 and o.pbl_blob.is_cuda:
+            layer.forward = types.MethodType(_folded_layer_forward, layer)
+            ne += 1
+    return n, ne
 
 
-def fuse_decode_(model: nn.Module, sets=FUSE_SETS, merge_batched: bool = False, prologues: bool = False) -> int:
+def fuse_decode_(model: nn.Module, sets=FUSE_SETS, merge_batched: bool = False, prologues: bool = False, epilogues: bool = False) -> int:
     """Decode-time fusion: in every module that holds all the projections of a set as PBLinears with one
     in_features (HF LlamaAttention: q/k/v_proj; LlamaMLP: gate/up_proj), replace them by members of one fused launch.
     7 launches per decoder layer become 4.  Returns the number of groups created.  The caller this serves is the token
@@ -380,7 +451,12 @@ def fuse_decode_(model: nn.Module, sets=FUSE_SETS, merge_batched: bool = False, 
     gate/up and down_proj are group-free fp16-exact PBLinears, fold the two RMSNorms into the q/k/v and gate/up launches and
     silu(gate) * up into the down_proj launch (their staging phases build the row they multiply): at <= 4 fp16 rows 18 small torch
     kernels per layer disappear and the linears stay 4 launches.  Every other call runs what the unfolded model runs.  The folded
-    layers are counted once at INFO level on the "pb_llm_amd" logger; the return value is the number of groups, as without it."""
+    layers are counted once at INFO level on the "pb_llm_amd" logger; the return value is the number of groups, as without it.
+    epilogues (OPT-IN; implies the prologue folding): a folded layer of type LlamaDecoderLayer with a LlamaAttention and a group-free
+    fp16-exact PBLinear o_proj also runs its decode step as six launches -- q/k/v (RMSNorm prologue), RoPE (one HIP launch instead of
+    HF's ~10 elementwise kernels), HF's cache update and attention, o_proj with the residual add in its store, gate/up (RMSNorm
+    prologue), down_proj (SwiGLU prologue and residual add) -- bit-identical to the prologues=True layer.  Every other call (more
+    rows, other dtypes, autograd, no position_embeddings) runs the prologues=True layer.  Counted at INFO level as well."""
     n = 0
     for mod in list(model.modules()):
         for names in sets:
@@ -393,11 +469,14 @@ def fuse_decode_(model: nn.Module, sets=FUSE_SETS, merge_batched: bool = False, 
             for i, (nm, m_) in enumerate(zip(names, subs)):
                 setattr(mod, nm, _FusedMember(grp, i, m_))
             n += 1
-    if prologues:
-        folded = _fold_prologues_(model)
+    if prologues or epilogues:
+        folded, with_epilogues = _fold_prologues_(model, epilogues)
         import logging
         logging.getLogger("pb_llm_amd").info("fuse_decode_(prologues=True): RMSNorm and SwiGLU folded into the decode launches of %d "
                                              "decoder layers", folded)
+        if epilogues:
+            logging.getLogger("pb_llm_amd").info("fuse_decode_(epilogues=True): RoPE and the residual adds folded into the decode "
+                                                 "launches of %d decoder layers", with_epilogues)
     return n
 
 

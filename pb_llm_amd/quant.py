@@ -903,26 +903,63 @@ class PBLinear(nn.Module, BinaryInterface):
         dd = torch.float16 if self.weight_dtype == torch.float16 else torch.float32
         return pb_linear_forward(self.packed, self.pbl_bias, x, dense_dtype=dd)
 
-    def forward_swiglu(self, gate_up: torch.Tensor, inter: int) -> torch.Tensor | None:
+    def forward_swiglu(self, gate_up: torch.Tensor, inter: int, residual: torch.Tensor | None = None) -> torch.Tensor | None:
         """self(silu(gate) * up) in ONE launch (pbl_linear_f16_swiglu: the GEMV builds its input row while it stages it) for
         gate_up [M, >= 2 inter] fp16 with gate at columns [0, inter) and up at [inter, 2 inter) -- the fused gate/up launch's output.
-        Returns [M, out_features] fp16, or None when the entry declines (column groups, more rows than one GEMV pass takes): the
-        caller then runs the unfused composition."""
+        residual (fp16, M rows of out_features, unit column stride): returns residual + self(silu(gate) * up) with HF's two roundings,
+        the add in the same launch's store (pbl_linear_f16_swiglu_residual).  Returns [M, out_features] fp16, or None when the entry
+        declines (column groups, more rows than one GEMV pass takes): the caller then runs the unfused composition."""
         if gate_up.dim() != 2 or gate_up.dtype != torch.float16 or not gate_up.is_cuda or gate_up.stride(-1) != 1 \
                 or inter != self.in_features or gate_up.shape[1] < 2 * inter:
             raise ValueError("forward_swiglu: gate_up must be an fp16 [M, >= 2 in_features] GPU tensor with unit column stride")
+        M = gate_up.shape[0]
+        r2 = None if residual is None else self._residual_rows(residual, M, gate_up.device)
         if self._image_only is not None or not self.pbl_blob.is_cuda or self.pbl_blob.device != gate_up.device:
             return None
-        M = gate_up.shape[0]
         ldx = gate_up.stride(0) if M > 1 else gate_up.shape[1]
         layer = self.packed.layer_struct(self.pbl_bias)
         y = torch.empty(M, self.out_features, dtype=torch.float16, device=gate_up.device)
-        rc = _lib.lib().pbl_linear_f16_swiglu(C.byref(layer), gate_up.data_ptr(), ldx, inter, y.data_ptr(), M, 0,
-                                              torch.cuda.current_stream(gate_up.device).cuda_stream)
+        st = torch.cuda.current_stream(gate_up.device).cuda_stream
+        if r2 is None:
+            rc = _lib.lib().pbl_linear_f16_swiglu(C.byref(layer), gate_up.data_ptr(), ldx, inter, y.data_ptr(), M, 0, st)
+        else:
+            rc = _lib.lib().pbl_linear_f16_swiglu_residual(C.byref(layer), gate_up.data_ptr(), ldx, inter, r2.data_ptr(),
+                                                           r2.stride(0) if M > 1 else self.out_features, y.data_ptr(), M, st)
         if rc == _lib.PBL_ERR_UNSUPPORTED:
             return None
         _lib.check(rc, "linear (SwiGLU prologue)")
         return y
+
+    def _residual_rows(self, residual: torch.Tensor, M: int, device) -> torch.Tensor:
+        """residual as the [M, out_features] view the residual epilogue reads (row stride free, unit column stride)"""
+        if residual.dtype != torch.float16 or residual.device != device or residual.shape[-1] != self.out_features \
+                or residual.numel() != M * self.out_features:
+            raise ValueError("residual must be an fp16 tensor of the output's shape on the activation's device")
+        r2 = residual.reshape(M, self.out_features)
+        if r2.stride(-1) != 1:
+            raise ValueError("residual must have a unit column stride")
+        return r2
+
+    def forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> torch.Tensor | None:
+        """residual + self(x) in ONE launch (pbl_linear_f16_residual: the add runs in the GEMV's store) with HF's roundings: the
+        linear's fp16 output, then the fp16 add.  x [..., in_features] fp16, residual fp16 of the output's shape.  Returns a
+        contiguous tensor of residual's shape, or None when the entry declines (column groups, more rows than one GEMV pass takes,
+        an image-only layer): the caller then runs `residual + self(x)`."""
+        if x.dtype != torch.float16 or not x.is_cuda or x.shape[-1] != self.in_features:
+            raise ValueError("forward_residual: x must be an fp16 [..., in_features] GPU tensor")
+        M = x.numel() // self.in_features
+        r2 = self._residual_rows(residual, M, x.device)
+        if self._image_only is not None or not self.pbl_blob.is_cuda or self.pbl_blob.device != x.device or M < 1:
+            return None
+        x2 = x.reshape(M, self.in_features).contiguous()
+        layer = self.packed.layer_struct(self.pbl_bias)
+        y = torch.empty(M, self.out_features, dtype=torch.float16, device=x.device)
+        rc = _lib.lib().pbl_linear_f16_residual(C.byref(layer), x2.data_ptr(), r2.data_ptr(), r2.stride(0) if M > 1 else self.out_features,
+                                                y.data_ptr(), M, torch.cuda.current_stream(x.device).cuda_stream)
+        if rc == _lib.PBL_ERR_UNSUPPORTED:
+            return None
+        _lib.check(rc, "linear (residual epilogue)")
+        return y.view(residual.shape)
 
     def to_regular_linear(self) -> nn.Linear:
         lin = nn.Linear(self.in_features, self.out_features, bias=self.pbl_bias is not None)

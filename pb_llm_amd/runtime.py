@@ -153,3 +153,60 @@ class FusedGemv:
     def algorithmic_bytes(self, M: int = 1) -> int:
         # x is read once for the group, not once per layer
         return sum(p.algorithmic_bytes(M, b is not None) for p, b in zip(self.packed, self.biases)) - 2 * M * self.K * (len(self.packed) - 1)
+
+
+_ROPE_LAYOUTS: dict = {}
+
+
+def _rope_layout(qkv: torch.Tensor, q_off: int, k_off: int, batch: int, seq: int, n_q: int, n_kv: int, head_dim: int,
+                 cos: torch.Tensor, sin: torch.Tensor):
+    """(shape, strides) of q_embed and k_embed as HF's apply_rotary_pos_emb returns them for the q / k views of qkv that a fused
+    q/k/v launch hands LlamaAttention -- found once per layout by running the same torch ops on meta tensors (TensorIterator's
+    stride rules, torch.cat's memory format) and cached"""
+    key = (batch, seq, n_q, n_kv, head_dim, qkv.stride(0), q_off, k_off, tuple(cos.shape), cos.stride(), sin.stride())
+    got = _ROPE_LAYOUTS.get(key)
+    if got is None:
+        def meta(t):
+            return torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device="meta")
+
+        def view(off, n):
+            return meta(qkv[:, off:off + n * head_dim].reshape(batch, seq, n * head_dim).view(batch, seq, -1, head_dim).transpose(1, 2))
+
+        c, s = meta(cos).unsqueeze(1), meta(sin).unsqueeze(1)
+        h = head_dim // 2
+        outs = [(x * c) + (torch.cat((-x[..., h:], x[..., :h]), dim=-1) * s) for x in (view(q_off, n_q), view(k_off, n_kv))]
+        got = _ROPE_LAYOUTS[key] = tuple((tuple(o.shape), tuple(o.stride())) for o in outs)
+    return got
+
+
+def rope_f16(qkv: torch.Tensor, q_off: int, k_off: int, batch: int, seq: int, n_q: int, n_kv: int, head_dim: int,
+             cos: torch.Tensor, sin: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor] | None:
+    """HF's apply_rotary_pos_emb(q, k, cos, sin) in ONE launch (pbl_rope_f16) for the q and k heads of a fused q/k/v output: qkv
+    [batch * seq, >= ...] fp16 with unit column stride holds n_q q heads from column q_off and n_kv k heads from column k_off
+    (head_dim each); cos / sin [1 or batch, 1 or seq, head_dim] fp16 (position_embeddings).  Returns (q_embed, k_embed) with
+    the values, shapes and strides HF's function gives for the views LlamaAttention makes of a fused launch's output -- or None
+    where the entry declines (odd head_dim, head_dim > 256) or cos / sin are not of that form: the caller then runs HF's."""
+    if qkv.dim() != 2 or qkv.dtype != torch.float16 or not qkv.is_cuda or qkv.stride(1) != 1 or qkv.shape[0] != batch * seq:
+        raise ValueError("rope_f16: qkv must be an fp16 [batch * seq, n] GPU tensor with unit column stride")
+    if min(q_off, k_off) < 0 or q_off + n_q * head_dim > qkv.shape[1] or k_off + n_kv * head_dim > qkv.shape[1]:
+        raise ValueError("rope_f16: the q / k heads must lie inside a row of qkv")
+    if cos.dtype != torch.float16 or sin.dtype != torch.float16 or cos.device != qkv.device or sin.device != qkv.device \
+            or cos.dim() != 3 or cos.shape != sin.shape or cos.stride() != sin.stride() or cos.stride(-1) != 1 \
+            or cos.shape[0] not in (1, batch) or cos.shape[1] not in (1, seq) or cos.shape[-1] != head_dim \
+            or head_dim % 2 or head_dim > 256:
+        return None
+    (qs, qst), (ks, kst) = _rope_layout(qkv, q_off, k_off, batch, seq, n_q, n_kv, head_dim, cos, sin)
+    if qst[3] != 1 or kst[3] != 1 or qs != (batch, n_q, seq, head_dim) or ks != (batch, n_kv, seq, head_dim):
+        return None
+    q = torch.empty_strided(qs, qst, dtype=torch.float16, device=qkv.device)
+    k = torch.empty_strided(ks, kst, dtype=torch.float16, device=qkv.device)
+    ld = qkv.stride(0) if qkv.shape[0] > 1 else qkv.shape[1]
+    rc = _lib.lib().pbl_rope_f16(qkv.data_ptr(), ld, q_off, k_off, batch, seq, n_q, n_kv, head_dim,
+                                 cos.data_ptr(), sin.data_ptr(), head_dim,
+                                 cos.stride(0) if cos.shape[0] > 1 else 0, cos.stride(1) if cos.shape[1] > 1 else 0,
+                                 q.data_ptr(), (C.c_int64 * 3)(*qst[:3]), k.data_ptr(), (C.c_int64 * 3)(*kst[:3]),
+                                 torch.cuda.current_stream(qkv.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "rope")
+    return q, k

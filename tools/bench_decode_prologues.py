@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Decode prologues (harness.fuse_decode_(prologues=True)) against fuse_decode_ alone on a llama-7b-shaped HF model (4096 / 11008 /
-32 heads), one token per forward, each mode captured in a hipGraph (GraphedForward) and replayed A/B/A/B in one process.
+"""Decode prologues (harness.fuse_decode_(prologues=True), mode "folded") and epilogues (fuse_decode_(epilogues=True), mode
+"epilogues") against fuse_decode_ alone (mode "plain") on a llama-7b-shaped HF model (4096 / 11008 / 32 heads), one token per
+forward, each mode captured in a hipGraph (GraphedForward) and replayed A/B/C/A/B/C in one process.
 Every decoder layer holds its OWN packed weights (~65 MB at 5 % salients): with 6 layers the weights exceed the 256 MiB Infinity Cache
 and a replay streams them from HBM.  The vocabulary is small (the head is a dense linear outside the comparison), so us per decoder
 layer = us per token / layers.  Kernels per token are counted with torch.profiler in a pass of their own, outside the timed window.
-  python tools/bench_decode_prologues.py [--layers 6] [--reps 7] [--iters 200] [--only folded]   (--only: rocprofv3 runs)"""
+  python tools/bench_decode_prologues.py [--layers 6] [--reps 7] [--iters 200] [--only folded]   (--only: rocprofv3 runs)
+The epilogues mode's logits are compared with the folded mode's (they must be equal: epilogues_logits_max_abs_diff)."""
 import argparse
 import copy
 import json
@@ -24,7 +26,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--layers", type=int, default=6)
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--iters", type=int, default=200)
-ap.add_argument("--only", choices=["plain", "folded"], default=None)
+ap.add_argument("--only", choices=["plain", "folded", "epilogues"], default=None)
 args = ap.parse_args()
 
 t_setup = time.time()
@@ -55,11 +57,14 @@ for layer in model.model.layers:                      # distinct packed weights 
 torch.cuda.empty_cache()
 plain = model
 folded = copy.deepcopy(model)
+epilogues = copy.deepcopy(model)
 H.fuse_decode_(plain)
 H.fuse_decode_(folded, prologues=True)
+H.fuse_decode_(epilogues, epilogues=True)
 nfold = sum(isinstance(m, H._FoldedMLP) for m in folded.modules())
+nepi = sum("forward" in vars(m) for m in epilogues.model.layers)
 ids = torch.randint(0, cfg.vocab_size, (1, 64), device="cuda")
-modes = {"plain": plain, "folded": folded}
+modes = {"plain": plain, "folded": folded, "epilogues": epilogues}
 if args.only:
     modes = {args.only: modes[args.only]}
 
@@ -102,15 +107,19 @@ def med(v):
 
 L = args.layers
 out = dict(model=f"llama-7b shape (4096 / 11008 / 32 heads), {L} decoder layers, distinct packed weights, 1 token, hipGraph replay",
-           packed_MB_per_decoder_layer=round(packed_bytes / L / 1e6, 1), layers_folded=nfold, reps=args.reps, iters=args.iters,
+           packed_MB_per_decoder_layer=round(packed_bytes / L / 1e6, 1), layers_folded=nfold, layers_epilogues=nepi, reps=args.reps, iters=args.iters,
            setup_s=round(setup_s, 1))
 for k in graphs:
     out[f"{k}_us_per_layer"] = round(med(times[k]) / L, 2)
     out[f"{k}_us_per_token"] = round(med(times[k]), 1)
     out[f"{k}_spread_pct"] = round(100 * (max(times[k]) - min(times[k])) / med(times[k]), 2)
     out[f"{k}_kernels_per_token"] = counts[k]
-if len(graphs) == 2:
+if "folded" in graphs and "plain" in graphs:
     a, b = logits["folded"], logits["plain"]
     out["logits_rel_max_diff"] = float((a - b).abs().max() / b.abs().max())
     out["folded_speedup"] = round(med(times["plain"]) / med(times["folded"]), 3)
+if "folded" in graphs and "epilogues" in graphs:
+    out["epilogues_logits_max_abs_diff"] = float((logits["epilogues"] - logits["folded"]).abs().max())
+    out["epilogues_logits_equal"] = bool(torch.equal(logits["epilogues"], logits["folded"]))
+    out["epilogues_saving_us_per_layer"] = round((med(times["folded"]) - med(times["epilogues"])) / L, 2)
 print(json.dumps(out))
