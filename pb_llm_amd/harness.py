@@ -13,7 +13,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .quant import PBLinear, replace_linear_with_pb
+from .quant import PBLinear, replace_linear_with_pb, tensor_version
 
 
 def find_layers(module: nn.Module, name: str = "") -> dict:
@@ -156,14 +156,14 @@ class _FusedMember(nn.Module):
         if g.norm is not None and g.norm.deferred(x):
             # folded decode (fuse_decode_(prologues=True)): x is the RAW hidden state its norm passed on unchanged; the launch
             # normalises it while it stages it
-            if g.x_ref is x and g.x_version == x._version and g.x_normed and self._index in g.pending:
+            if g.x_ref is x and g.x_version == tensor_version(x) and g.x_normed and self._index in g.pending:
                 g.pending.discard(self._index)
                 g.served += 1
             else:
                 g.launch(x, rows, self._index, norm=True)
             return g.outs[self._index].reshape(*x.shape[:-1], self.out_features)
-        if not x.is_cuda or (torch.is_grad_enabled() and x.requires_grad):
-            return self.own(x)
+        if not x.is_cuda or x.is_inference() or (torch.is_grad_enabled() and x.requires_grad):
+            return self.own(x)          # (an inference tensor has no version counter: nothing may be reused across calls)
         fused_ok = rows <= 4 and (x.dtype == torch.float16 or (x.dtype == torch.bfloat16 and g.fused.bf16_ok))
         # batched decode (5 .. MERGE_MAX_ROWS rows, any activation dtype): ONE call of the row-wise concatenation of the members
         # (packing.concat_rows: a record is 16 rows with everything it needs inside it) instead of one small-batch launch + reduce
@@ -171,7 +171,7 @@ class _FusedMember(nn.Module):
         merged_ok = not fused_ok and g.merge_batched and 4 < rows <= g.MERGE_MAX_ROWS
         if not (fused_ok or merged_ok):
             return self.own(x)
-        if g.x_ref is x and g.x_version == x._version and not g.x_normed and self._index in g.pending:   # each launch serves each member once
+        if g.x_ref is x and g.x_version == tensor_version(x) and not g.x_normed and self._index in g.pending:   # each launch serves each member once
             g.pending.discard(self._index)
             g.served += 1
             return g.outs[self._index].reshape(*x.shape[:-1], self.out_features)
@@ -198,7 +198,7 @@ class _FusedGroup:
         self._build()
 
     def _stamp(self):
-        return tuple((m.pbl_blob.data_ptr(), m.pbl_blob._version, None if m.pbl_bias is None else m.pbl_bias.data_ptr())
+        return tuple((m.pbl_blob.data_ptr(), m._blob_version(), None if m.pbl_bias is None else m.pbl_bias.data_ptr())
                      for m in self.mods)
 
     def _build(self):
@@ -253,7 +253,7 @@ class _FusedGroup:
                 y = self.fused.run(x2)
             self.y_all = y
             self.outs = [y[:, int(self.fused.offs[i]):int(self.fused.offs[i + 1])] for i in range(len(self.mods))]
-        self.x_ref, self.x_version, self.x_normed = x, x._version, norm
+        self.x_ref, self.x_version, self.x_normed = x, tensor_version(x), norm
         self.pending = set() if index is None else set(range(len(self.mods))) - {index}
         self.launches += 1
 
@@ -275,11 +275,13 @@ class _FusedGroup:
 FUSE_SETS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))     # LLaMA naming (HF)
 
 
-def _prologue_ok(x: torch.Tensor, weight: torch.Tensor) -> bool:
+def _prologue_ok(x: torch.Tensor, weight: torch.Tensor, stateless: bool = False) -> bool:
     """THE predicate of the folded decode path (fuse_decode_(prologues=True)): a deferring norm passes x on unchanged exactly when it
-    holds, and the fused group it feeds evaluates it again on the same tensor -- fp16 on the GPU, at most 4 rows, no autograd"""
+    holds, and the fused group it feeds evaluates it again on the same tensor -- fp16 on the GPU, at most 4 rows, no autograd, and
+    not an inference tensor (the hand-over is keyed on the version counter, which those lack).  stateless: the caller keeps nothing
+    between calls (the epilogues=True folded layer), so inference tensors qualify."""
     return (x.is_cuda and x.dtype == torch.float16 and x.dim() >= 1 and 1 <= x.numel() // max(x.shape[-1], 1) <= 4
-            and weight.dtype == torch.float16 and weight.device == x.device
+            and weight.dtype == torch.float16 and weight.device == x.device and (stateless or not x.is_inference())
             and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)))
 
 
@@ -304,14 +306,14 @@ class _DeferredNorm(nn.Module):
 
     def forward(self, x):
         if _prologue_ok(x, self.norm.weight):
-            self.x_ref, self.x_version = x, x._version        # (held until the next call: the identity cannot be a recycled address)
+            self.x_ref, self.x_version = x, tensor_version(x)   # (held until the next call: the identity cannot be a recycled address)
             return x
         self.x_ref = None
         return self.norm(x)
 
     def deferred(self, x) -> bool:
         """x is what this norm passed on un-normalised (and the predicate still holds for it)"""
-        return self.x_ref is x and self.x_version == x._version and _prologue_ok(x, self.norm.weight)
+        return self.x_ref is x and self.x_version == tensor_version(x) and _prologue_ok(x, self.norm.weight)
 
 
 class _FoldedMLP(nn.Module):
@@ -349,7 +351,7 @@ def _folded_layer_forward(self, hidden_states, attention_mask=None, position_ids
     down_proj with the SwiGLU prologue and the residual add -- every step with HF's roundings, so the result equals the
     prologues=True layer's bit for bit.  Every other call runs LlamaDecoderLayer.forward (the prologues=True layer)."""
     d_in = self.input_layernorm
-    if position_embeddings is None or hidden_states.dim() != 3 or not _prologue_ok(hidden_states, d_in.norm.weight):
+    if position_embeddings is None or hidden_states.dim() != 3 or not _prologue_ok(hidden_states, d_in.norm.weight, stateless=True):
         return type(self).forward(self, hidden_states, attention_mask=attention_mask, position_ids=position_ids,
                                   past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings, **kwargs)
     from transformers.models.llama import modeling_llama as ML
@@ -537,8 +539,9 @@ def drop_gemm_images_(model: nn.Module) -> int:
     build_gemm_images_: with the round-5 defaults every fp16-exact linear gets an image on its first call with 5 rows or more
     (1.7 - 2.4 x the blob's bytes; 4.2 GB for a 7B model at 5 % hessian salients), which a decode-only phase at batch <= 4 never
     reads.  The next call that wants an image rebuilds it.  Not while a captured graph that uses the images may still be replayed.
-    Returns the bytes released."""
+    Also forgets the kept fragment-major copy of the last activation (quant.drop_x_fragments_).  Returns the bytes released."""
     from . import quant as Q
+    Q.drop_x_fragments_()
     n = 0
     for m in model.modules():
         if isinstance(m, Q.PBLinear):

@@ -202,6 +202,8 @@ class P2PAllReduce:
                                                         out_f16.data_ptr() if out_f16 is not None else None, t.numel(),
                                                         self.max_numel, st), "p2p_allreduce")
         self._phase_end("p2p_allreduce", ev)
+        # written through raw pointers: bump the version counters, so that caches keyed on them (quant.x_fragments) see the write
+        torch.autograd.graph.increment_version([t] if out_f16 is None else [t, out_f16])
         return t
 
     def _phase_start(self):
@@ -282,6 +284,7 @@ class P2PAllReduce:
         _lib.check(L.pbl_p2p_reduce_f32_dev(self._ptrs, self.rank, self.world, out.data_ptr() if f32 else None,
                                             None if f32 else out.data_ptr(), M * packed.N, self.max_numel, packed.NRB, st), "p2p_reduce")
         self._phase_end("reduce", ev)
+        torch.autograd.graph.increment_version(out)        # (a raw-pointer write: see all_reduce_)
         return True
 
     def check(self) -> None:

@@ -50,6 +50,7 @@ def quant8_rows_(W: torch.Tensor):
     sc = torch.empty(N, dtype=torch.float32, device=W.device)
     zp = torch.empty(N, dtype=torch.float32, device=W.device)
     _lib.check(_lib.lib().pbl_quant8_rows(W.data_ptr(), _DT[W.dtype], N, K, sc.data_ptr(), zp.data_ptr(), _stream(W)), "quant8_rows")
+    torch.autograd.graph.increment_version(W)           # W was written through its pointer: caches keyed on its version must see it
     return sc, zp
 
 

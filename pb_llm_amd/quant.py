@@ -16,7 +16,9 @@ elementwise work, library GEMMs).  There is no CPU fallback: a CPU tensor raises
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -96,31 +98,62 @@ GEMM_X_FRAGMENTS = os.environ.get("PBL_GEMM_X_FRAGMENTS", "1") != "0"
 # round 6: the GEMM-image kernel reads x from a FRAGMENT-MAJOR copy (pbl_x_to_fragments: one small kernel per distinct x) instead of
 # staging 256-token tiles through LDS -- a quarter of a round went into that staging (profiles/r06_gemm.md).  The copy of the LAST
 # activation tensor is kept per device (q / k / v and gate / up of a decoder layer are called with the same tensor object:
-# gptq_pb/eval_ppl_utils.py:55-64), keyed on the tensor OBJECT and its version -- the tensor is held, so its address cannot be reused
-# by other data while the entry lives.  False: the round-4 kernel (x tiles by LDS-DMA); the results are bit-identical.
-_XF_CACHE: dict = {}        # device index -> (x tensor, version, stream, fragments)
+# gptq_pb/eval_ppl_utils.py:55-64), keyed on the tensor OBJECT (held by a weak reference: the entry goes when the tensor dies, so
+# neither x nor its copy is kept alive), its data pointer and its version counter.  False: the round-4 kernel (x tiles by LDS-DMA);
+# the results are bit-identical.
+# Caveat: the key sees writes that bump the version counter -- torch in-place ops, and the library's own raw-pointer writers
+# (P2PAllReduce.all_reduce_, fused_linear_, prep.quant8_rows_ bump it).  It cannot see writes by a replayed hipGraph, by foreign code
+# through data_ptr(), or through `t.data` (a fresh counter): after such a write into an activation that is called again, call
+# drop_x_fragments_().  Inference tensors (torch.inference_mode) have no version counter and are never cached.
+_XF_CACHE: dict = {}        # device index -> (weakref to the x tensor, version, data_ptr, stream, (fragments, shape))
+
+
+def tensor_version(t: torch.Tensor, generation: int = 0) -> tuple:
+    """THE read of a tensor's version counter in this package: every cache key that trusts a counter goes through here.  Returns
+    (generation, t._version).  Inference tensors (made under torch.inference_mode: activations, and weights that were loaded, built
+    or moved there) have no counter and count as version -1; what changes then is `generation`, the owning module's reload counter,
+    which its load_state_dict bumps (PBLinear, _DenseBacked).  So a reload is always seen, but a direct in-place write into an
+    inference-tensor weight inside inference_mode is NOT: reload the module (or call _DenseBacked.invalidate()) after one.
+    Activations that are inference tensors feed no cross-call reuse at all (x_fragments, harness.fuse_decode_'s bookkeeping)."""
+    return (generation, -1 if t.is_inference() else t._version)
+
+
+def _blob_key(packed: PackedWeight) -> tuple:
+    """what a GEMM image / salient list kept on a PackedWeight is keyed on (a reload makes a new PackedWeight: PBLinear.packed)"""
+    return (packed.blob.data_ptr(), tensor_version(packed.blob))
+
+
+def _xf_drop_entry(idx: int, ref) -> None:
+    """weakref callback: the activation of the kept copy died -- release the copy with it"""
+    hit = _XF_CACHE.get(idx)
+    if hit is not None and hit[0] is ref:
+        del _XF_CACHE[idx]
 
 
 def x_fragments(x2: torch.Tensor, cache_key: "torch.Tensor | None" = None) -> torch.Tensor:
     """pbl_x_to_fragments of x2 [M, K] fp16 (contiguous rows); with cache_key (the caller's ORIGINAL activation tensor) the copy of the
-    last tensor per device is reused while that tensor object is unchanged (same object, same version, same stream)."""
+    last tensor per device is reused while that tensor object is alive and unchanged (same object, data pointer, version and stream).
+    An inference tensor as cache_key is not cached (no version counter: nothing would see a write between two calls)."""
     dev = x2.device
     cur = torch.cuda.current_stream(dev)
-    if cache_key is not None and not torch.cuda.is_current_stream_capturing():
+    keep = cache_key is not None and not cache_key.is_inference() and not torch.cuda.is_current_stream_capturing()
+    if keep:
         hit = _XF_CACHE.get(dev.index)
-        if hit is not None and hit[0] is cache_key and hit[1] == cache_key._version and hit[2] == cur.cuda_stream and hit[3][1] == tuple(x2.shape):
-            return hit[3][0]
+        if hit is not None and hit[0]() is cache_key and hit[1] == tensor_version(cache_key) and hit[2] == cache_key.data_ptr() \
+                and hit[3] == cur.cuda_stream and hit[4][1] == tuple(x2.shape):
+            return hit[4][0]
     M, K = x2.shape
     L = _lib.lib()
     xf = torch.empty(int(L.pbl_x_fragment_bytes(M, K)), dtype=torch.uint8, device=dev)
     _lib.check(L.pbl_x_to_fragments(x2.data_ptr(), M, K, K if M == 1 else x2.stride(0), xf.data_ptr(), cur.cuda_stream), "x_to_fragments")
-    if cache_key is not None and not torch.cuda.is_current_stream_capturing():
-        _XF_CACHE[dev.index] = (cache_key, cache_key._version, cur.cuda_stream, (xf, tuple(x2.shape)))
+    if keep:
+        ref = weakref.ref(cache_key, functools.partial(_xf_drop_entry, dev.index))
+        _XF_CACHE[dev.index] = (ref, tensor_version(cache_key), cache_key.data_ptr(), cur.cuda_stream, (xf, tuple(x2.shape)))
     return xf
 
 
 def drop_x_fragments_() -> None:
-    """forget the kept fragment copies (and the activation tensors they hold alive)"""
+    """forget the kept fragment copies"""
     _XF_CACHE.clear()
 
 
@@ -331,7 +364,7 @@ def _image_fills_the_chip(N: int, M: int, device) -> bool:
 
 def _kept_image(packed: PackedWeight) -> GemmImage | None:
     """the layer's GEMM image, built on first use and kept with the PackedWeight until its blob changes (GEMM_KEEP_IMAGE)"""
-    key = (packed.blob.data_ptr(), packed.blob._version)
+    key = _blob_key(packed)
     kept = getattr(packed, "_gemm_image", None)
     if kept is None or kept[0] != key:
         if torch.cuda.is_current_stream_capturing():
@@ -351,7 +384,7 @@ def _kept_images_f32grid(packed: PackedWeight) -> "tuple[GemmImage, GemmImage] |
     the PackedWeight until its blob changes; None: the layer has no image (or the build runs under stream capture)"""
     if packed.flags & _lib.PBL_FLAG_SAL_F16 or not fused_gemm_ok(packed):
         return None
-    key = (packed.blob.data_ptr(), packed.blob._version)
+    key = _blob_key(packed)
     kept = getattr(packed, "_gemm_images_f32", None)
     if kept is None or kept[0] != key:
         if torch.cuda.is_current_stream_capturing():
@@ -410,12 +443,12 @@ def _small_batch_image(packed: PackedWeight) -> GemmImage | None:
     if SMALL_BATCH_IMAGE == "1":
         return _kept_image(packed)
     kept = getattr(packed, "_gemm_image", None)
-    return kept[1] if kept is not None and kept[0] == (packed.blob.data_ptr(), packed.blob._version) else None
+    return kept[1] if kept is not None and kept[0] == _blob_key(packed) else None
 
 
 def _kept_list(packed: PackedWeight) -> torch.Tensor | None:
     """the layer's salient list, built on first use and kept with the PackedWeight until its blob changes (GEMM_KEEP_LIST)"""
-    key = (packed.blob.data_ptr(), packed.blob._version)
+    key = _blob_key(packed)
     kept = getattr(packed, "_gemm_list", None)
     if kept is None or kept[0] != key:
         kept = (key, gemm_list(packed))
@@ -717,12 +750,13 @@ def _(blob, bias, x, meta, dense_f16, out_f32):
 class PBLinear(nn.Module, BinaryInterface):
     """Packed partially-binarized linear layer.  Holds the PBL1 blob as a buffer so
     .to(device) / state_dict() work; `weight` is a dense view materialised on demand."""
+    _generation = 0                      # bumped by every load_state_dict: what tells a reload of an inference-tensor blob apart
 
     def __init__(self, packed: PackedWeight, bias: torch.Tensor | None = None, dtype=torch.float16):
         super().__init__()
         self.in_features, self.out_features = packed.K, packed.N
         self._meta = packed
-        self._meta_version = packed.blob._version
+        self._meta_version = tensor_version(packed.blob, self._generation)
         self.register_buffer("pbl_blob", packed.blob)
         self.register_buffer("pbl_bias", bias.detach().float().clone() if bias is not None else None)
         self.weight_dtype = dtype
@@ -735,6 +769,14 @@ class PBLinear(nn.Module, BinaryInterface):
         st = dict(self.__dict__)
         st["_image_only"] = None
         return st
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        """a reload is seen by `packed` (and the fused launches' stamps) even where the blob has no version counter (inference tensor)"""
+        self._generation += 1
+        super()._load_from_state_dict(*args, **kwargs)
+
+    def _blob_version(self, blob: torch.Tensor | None = None) -> tuple:
+        return tensor_version(self.pbl_blob if blob is None else blob, self._generation)
 
     # -- one copy of the weights on the device (round 6; VERDICT r5 item 5) --------------------------------------------------------
     def release_blob_(self, pin: bool = False) -> int:
@@ -759,8 +801,8 @@ class PBLinear(nn.Module, BinaryInterface):
             host = host.pin_memory()
         self.pbl_blob = host
         self._meta = PackedWeight(host, p.N, p.K, p.P, p.G, p.NRB, p.flags, p.max_nch, p.max_nexc, p.nnz, p.nexc)
-        self._meta_version = host._version
-        self._image_only = (img, host._version)
+        self._meta_version = self._blob_version(host)
+        self._image_only = (img, self._meta_version)
         return nbytes
 
     def restore_blob_(self, device=None) -> None:
@@ -769,13 +811,13 @@ class PBLinear(nn.Module, BinaryInterface):
             return
         img, ver = self._image_only
         dev = torch.device(device) if device is not None else img.data.device
-        blob = self.pbl_blob.to(dev)
-        p = self._meta
+        p = self.packed                                      # (the header of what the host buffer holds NOW: load_state_dict may have rewritten it)
+        blob = p.blob.to(dev)
         self.pbl_blob = blob
         self._meta = PackedWeight(blob, p.N, p.K, p.P, p.G, p.NRB, p.flags, p.max_nch, p.max_nexc, p.nnz, p.nexc)
-        self._meta_version = blob._version
-        if ver == p.blob._version and blob.device == img.data.device:
-            self._meta._gemm_image = ((blob.data_ptr(), blob._version), img)
+        self._meta_version = self._blob_version(blob)
+        if ver == self._blob_version(p.blob) and blob.device == img.data.device:
+            self._meta._gemm_image = (_blob_key(self._meta), img)
         self._image_only = None
 
     def _image_only_forward(self, x):
@@ -784,13 +826,13 @@ class PBLinear(nn.Module, BinaryInterface):
             return self.forward(x)
         img, ver = self._image_only
         p = self.packed                                      # (re-validates a blob load_state_dict wrote into the host buffer)
-        if p.blob._version != ver:
+        if self._blob_version(p.blob) != ver:
             # the weights changed under the image: rebuild it from a transient device copy of the new blob (stream ordered)
             tmp = PackedWeight(p.blob.to(img.data.device), p.N, p.K, p.P, p.G, p.NRB, p.flags, p.max_nch, p.max_nexc, p.nnz, p.nexc)
             img = gemm_image(tmp)
             if img is None:
                 raise _lib.PblError("image-only layer: the loaded weights have no GEMM image; call restore_blob_()")
-            self._image_only = (img, p.blob._version)
+            self._image_only = (img, self._blob_version(p.blob))
         if torch.is_grad_enabled() and x.requires_grad:
             raise _lib.PblError("image-only layer: the input gradient unpacks the blob; call restore_blob_() before training through it")
         x = _autocast_input(x)
@@ -862,16 +904,17 @@ class PBLinear(nn.Module, BinaryInterface):
     @property
     def packed(self) -> PackedWeight:
         m = self._meta
-        if self.pbl_blob._version != self._meta_version:
+        ver = self._blob_version()
+        if ver != self._meta_version:
             # written in place (load_state_dict copies into the buffer): the header fields the kernels size their
             # LDS with (max_nch, max_nexc, flags) must come from the NEW blob, which is validated again
             m = PackedWeight.from_blob(self.pbl_blob)
             if (m.N, m.K) != (self.out_features, self.in_features):
                 raise _lib.PblError(f"loaded blob is {m.N}x{m.K}, module is {self.out_features}x{self.in_features}")
-            self._meta, self._meta_version = m, self.pbl_blob._version
+            self._meta, self._meta_version = m, ver
         elif m.blob is not self.pbl_blob:  # the buffer moved (.to / .cuda)
             m = PackedWeight(self.pbl_blob, m.N, m.K, m.P, m.G, m.NRB, m.flags, m.max_nch, m.max_nexc, m.nnz, m.nexc)
-            self._meta, self._meta_version = m, self.pbl_blob._version
+            self._meta, self._meta_version = m, ver
         return m
 
     @property
@@ -1031,15 +1074,22 @@ def _autocast_input(x: torch.Tensor) -> torch.Tensor:
 
 class _DenseBacked(nn.Module, BinaryInterface):
     """Shared plumbing: keeps the reference's `weight`/`bias` Parameters and packs lazily."""
+    _generation = 0                      # bumped by every load_state_dict (see tensor_version)
 
     def _pack(self) -> PackedWeight:
         raise NotImplementedError
 
     def _cache_key(self):
-        """Everything the packed blob was derived from: a `weight.data` edit, load_state_dict, .half()/.float() or a new
-        mask / scale changes the key, so a stale blob is never served."""
+        """Everything the packed blob was derived from.  Seen: an in-place op on the Parameter (`w.copy_()` under no_grad, an
+        optimizer step), `.data =` reassignment, load_state_dict, .half()/.float()/.to(), a new mask / scale object.  NOT seen: an
+        in-place edit through `weight.data` (`w.data.copy_()`, `w.data[...] = ...`: `.data` has a version counter of its own), a write
+        through data_ptr() by foreign code, or an in-place write into an inference-tensor weight -- call invalidate() after those."""
         w = self.weight
-        return (w.data_ptr(), w._version, w.dtype, tuple(w.shape))
+        return (w.data_ptr(), tensor_version(w, self._generation), w.dtype, tuple(w.shape))
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._generation += 1                # (a reload must change the key also where the weight has no version counter)
+        super()._load_from_state_dict(*args, **kwargs)
 
     def _packed_on(self, device) -> PackedWeight:
         p, key = getattr(self, "_packed", None), self._cache_key()
@@ -1185,8 +1235,8 @@ class BinaryXnorExceptOutliersLinear(_DenseBacked):
 
     def _cache_key(self):
         s, m = self.binary_scale, self.outlier_mask
-        return super()._cache_key() + (None if m is None else (m.data_ptr(), m._version),
-                                       None if s is None else (s.data_ptr(), s._version), float(self.outlier_scale))
+        return super()._cache_key() + (None if m is None else (m.data_ptr(), tensor_version(m)),
+                                       None if s is None else (s.data_ptr(), tensor_version(s)), float(self.outlier_scale))
 
     def gen_outlier_mask(self):
         with torch.no_grad():

@@ -341,6 +341,24 @@ def _tp_worker(rank, world, port, collective, out):
                     same = same and bool(torch.equal(ya, mod(xi))) and bool(torch.equal(yb, mod2(xi * 0.5)))
             rel2, ratio2 = O.parity_errors(yb.float().cpu().numpy(), O.dense_linear((xs * 0.5).cpu().numpy(), W2q.numpy()))
             same = same and rel2 < 1e-3 and ratio2 < 1.0
+            # all_reduce_ writes t and out_f16 through raw pointers and bumps their version counters, so that an activation summed
+            # into a reused buffer is not served from a stale fragment-major copy (quant.x_fragments): 80 fp16 rows through a layer
+            # with a GEMM image, new partials all-reduced into the same buffer, the layer again
+            Wk = synth.llm_weight(64, 128, seed=45, heavy_tail=True)
+            maskk = O.ptq_low_mask(Wk, 0.9, "magnitude", None, -1)
+            rk = O.ptq_rtn(Wk, maskk, 8, -1)
+            Wk16 = torch.from_numpy(rk["W_fq"]).half()
+            lay = Q.PBLinear.from_dense(Wk16, None, torch.from_numpy(maskk), -1, rk["hscale"], rk["hzero"]).to(dev)
+            out16 = torch.empty(80, 128, dtype=torch.float16, device=dev)
+            for it in range(2):
+                t = torch.from_numpy(synth.activations((80, 128), 70 + 2 * rank + it, 21)).float().to(dev)
+                v0 = (t._version, out16._version)
+                mod.comm.all_reduce_(t, out16)
+                same = same and t._version > v0[0] and out16._version > v0[1]
+                with torch.no_grad():
+                    yk = lay(out16)
+                rk_, qk_ = O.parity_errors(yk.float().cpu().numpy(), O.dense_linear(out16.float().cpu().numpy(), Wk16.float().numpy()))
+                same = same and rk_ < 1e-3 and qk_ < 1.0
             mod.comm.check()
             mod.comm.close()
         out[rank] = (rel, ratio, same)
