@@ -511,6 +511,30 @@ int pbl_rope_f16(const void* qkv, uint32_t ld, uint32_t q_off, uint32_t k_off, i
                  const void* cos, const void* sin, int cos_dim, int64_t cos_sb, int64_t cos_ss,
                  void* q_out, const int64_t* q_ostride, void* k_out, const int64_t* k_ostride, void* stream);
 
+/* Decode attention over a static KV cache (csrc/pbl_attn.hip; harness.DecodeSession / harness.generate).
+ *   The cache of a layer: k_cache / v_cache [B, Hkv, max_len, D] fp16, contiguous, 16-B aligned (HF StaticLayer.keys / .values), and
+ *   pos, a DEVICE int64: the number of rows already written (StaticLayer.cumulative_length).  The position is read on the device
+ *   only, so one captured graph serves every position.
+ *   pbl_rope_append_f16   pbl_rope_f16 on the q heads (same arguments, same q_out layout and bits), and in the same launch the k heads
+ *                         rotated (the bits of pbl_rope_f16's k) and the v heads (column v_off of qkv) unchanged into cache rows
+ *                         [pos, pos + S) of every sequence; rows at or beyond max_len are not written.  pos is not changed.
+ *   pbl_decode_attn_f16   out [B S, ldo] fp16 (row b S + s, head h at column h D): query row s of q (element (b, h, s, d) at b q_stride[0]
+ *                         + h q_stride[1] + s q_stride[2] + d; host array of 3) attends to cache rows [0, pos + s] of its kv head h / (Hq /
+ *                         Hkv): softmax(scaling q k^T) v in fp32, rounded to fp16 once.  Rows beyond pos + S are never read.  Two
+ *                         launches (per-split partials into ws, then their combine in split order: bit-stable); the second advances
+ *                         *pos by S.  ws: pbl_decode_attn_workspace_bytes(B, S, Hq, D, max_len) bytes, 16-B aligned.
+ * Both: PBL_ERR_INVALID_ARG for NULL pointers, sizes < 1, negative strides and outputs overlapping inputs, before any device work;
+ * PBL_ERR_UNSUPPORTED unless D is 64 or 128, S <= 4, B <= 4 and Hkv divides Hq (and max_len <= 65536 for the attention).  No
+ * allocation, no synchronisation: capturable in a hipGraph. */
+int pbl_rope_append_f16(const void* qkv, uint32_t ld, uint32_t q_off, uint32_t k_off, uint32_t v_off, int B, int S, int Hq, int Hkv,
+                        int D, const void* cos, const void* sin, int cos_dim, int64_t cos_sb, int64_t cos_ss,
+                        void* q_out, const int64_t* q_ostride, void* k_cache, void* v_cache, int max_len, const int64_t* pos,
+                        void* stream);
+size_t pbl_decode_attn_workspace_bytes(int B, int S, int Hq, int D, int max_len);
+int pbl_decode_attn_f16(const void* q, const int64_t* q_stride, const void* k_cache, const void* v_cache, int B, int S, int Hq,
+                        int Hkv, int D, int max_len, float scaling, int64_t* pos, void* out, uint32_t ldo, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* ---------------- QAT step, weight side ------------------------------------------ */
 /* The elementwise work of one training step of BinaryXnorExceptOutliersLinear
  * (quant/outlier_quantizer.py:83-99; straight-through estimator quant/quantizer.py:18-25), fused into

@@ -60,7 +60,8 @@ EXPORTS = ["pbl_status_string", "pbl_version", "pbl_pack_dense_f32", "pbl_pack_d
            "pbl_gemm_f16_image_ex", "pbl_act_bf16_prepare", "pbl_act_finish",
            "pbl_linear_bf16", "pbl_gemv_bf16_fused_host", "pbl_gemm_image_workspace_bytes", "pbl_gemm_image_plan",
            "pbl_gemm_f16_image_ws", "pbl_gemv_f16_fused_norm_host", "pbl_linear_f16_swiglu",
-           "pbl_linear_f16_residual", "pbl_linear_f16_swiglu_residual", "pbl_rope_f16"]
+           "pbl_linear_f16_residual", "pbl_linear_f16_swiglu_residual", "pbl_rope_f16",
+           "pbl_rope_append_f16", "pbl_decode_attn_workspace_bytes", "pbl_decode_attn_f16"]
 
 
 def lib() -> C.CDLL:
@@ -227,6 +228,14 @@ def lib() -> C.CDLL:
     L.pbl_rope_f16.restype = C.c_int
     L.pbl_rope_f16.argtypes = [vp, u32, u32, u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64, C.c_int64,
                                vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp]
+    L.pbl_rope_append_f16.restype = C.c_int
+    L.pbl_rope_append_f16.argtypes = [vp, u32, u32, u32, u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64,
+                                      C.c_int64, vp, C.POINTER(C.c_int64), vp, vp, C.c_int, vp, vp]
+    L.pbl_decode_attn_workspace_bytes.restype = sz
+    L.pbl_decode_attn_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.pbl_decode_attn_f16.restype = C.c_int
+    L.pbl_decode_attn_f16.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      vp, vp, u32, vp, sz, vp]
     _lib = L
     return L
 

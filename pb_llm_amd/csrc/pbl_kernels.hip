@@ -1370,6 +1370,53 @@ __global__ __launch_bounds__(256) void pbl_rope_kernel(RopeArgs a) {
     out[i + a.half] = __builtin_bit_cast(uint16_t, o2);
 }
 
+// ---- RoPE + static KV-cache append of a decode step (pbl_rope_append_f16) ------------------------------------------------------
+struct RopeAppendArgs {
+    RopeArgs r;                     // q / k as in pbl_rope_kernel (r.k_out unused); r.H = Hq + 2 Hkv: the v heads follow the k heads
+    uint16_t* k_cache;              // [B, Hkv, max_len, D] fp16
+    uint16_t* v_cache;
+    const int64_t* pos;             // the layer's position: token (b, s) goes to cache row pos + s
+    uint32_t v_off;
+    int Hkv, max_len;
+};
+
+// pbl_rope_kernel's arithmetic for the q and k heads (the same roundings, bit for bit); k goes to cache row pos + s instead of a
+// fresh tensor, and the v heads are copied there unchanged.  The position is read on the device: one captured graph serves every
+// position.  Rows at or beyond max_len are not written.
+__global__ __launch_bounds__(256) void pbl_rope_append_kernel(RopeAppendArgs a) {
+#pragma clang fp contract(off)
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= a.r.pairs) return;
+    const int i = idx % a.r.half, t = idx / a.r.half;
+    const int h = t % a.r.H, m = t / a.r.H;
+    const int b = m / a.r.S, s = m - b * a.r.S;
+    const int D = 2 * a.r.half;
+    const int64_t row = *a.pos + s;
+    if (h >= a.r.Hq + a.Hkv) {                                              // a v head: copied as it is
+        const int hh = h - a.r.Hq - a.Hkv;
+        if (row < 0 || row >= a.max_len) return;
+        const uint16_t* x = a.r.qkv + size_t(m) * a.r.ld + a.v_off + size_t(hh) * D;
+        uint16_t* out = a.v_cache + ((size_t(b) * a.Hkv + hh) * a.max_len + row) * D;
+        out[i] = x[i];
+        out[i + a.r.half] = x[i + a.r.half];
+        return;
+    }
+    const bool isq = h < a.r.Hq;
+    const int hh = isq ? h : h - a.r.Hq;
+    if (!isq && (row < 0 || row >= a.max_len)) return;
+    const uint16_t* x = a.r.qkv + size_t(m) * a.r.ld + (isq ? a.r.q_off : a.r.k_off) + size_t(hh) * D;
+    const int64_t crow = b * a.r.c_sb + s * a.r.c_ss;
+    const float x1 = float(__builtin_bit_cast(_Float16, x[i])), x2 = float(__builtin_bit_cast(_Float16, x[i + a.r.half]));
+    const float c1 = float(__builtin_bit_cast(_Float16, a.r.cos[crow + i])), c2 = float(__builtin_bit_cast(_Float16, a.r.cos[crow + i + a.r.half]));
+    const float s1 = float(__builtin_bit_cast(_Float16, a.r.sin[crow + i])), s2 = float(__builtin_bit_cast(_Float16, a.r.sin[crow + i + a.r.half]));
+    const _Float16 o1 = _Float16(mul_f16(x1, c1) + mul_f16(-x2, s1));      // rotate_half: (-x2, x1); fp32 sum, one rounding
+    const _Float16 o2 = _Float16(mul_f16(x2, c2) + mul_f16(x1, s2));
+    uint16_t* out = isq ? a.r.q_out + (b * a.r.q_ob + hh * a.r.q_oh + s * a.r.q_os)
+                        : a.k_cache + ((size_t(b) * a.Hkv + hh) * a.max_len + row) * D;
+    out[i] = __builtin_bit_cast(uint16_t, o1);
+    out[i + a.r.half] = __builtin_bit_cast(uint16_t, o2);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1635,6 +1682,53 @@ int pbl_rope_f16(const void* qkv, uint32_t ld, uint32_t q_off, uint32_t k_off, i
     a.pairs = int(M * (Hq + Hkv) * (D / 2));
     void* argv[] = {&a};
     return hipLaunchKernel(reinterpret_cast<const void*>(pbl_rope_kernel), dim3((a.pairs + 255) / 256), dim3(256), argv, 0,
+                           static_cast<hipStream_t>(stream)) == hipSuccess ? PBL_OK : PBL_ERR_LAUNCH;
+}
+
+// pbl_rope_f16 for q, and k / v appended to a layer's static KV cache in the same launch (pbl_rope_append_kernel).  Scope of the
+// decode-attention path (pbl_decode_attn_f16): PBL_ERR_UNSUPPORTED unless D is 64 or 128, S <= 4, B <= 4 and Hkv divides Hq.
+int pbl_rope_append_f16(const void* qkv, uint32_t ld, uint32_t q_off, uint32_t k_off, uint32_t v_off, int B, int S, int Hq, int Hkv,
+                        int D, const void* cos, const void* sin, int cos_dim, int64_t cos_sb, int64_t cos_ss,
+                        void* q_out, const int64_t* q_ostride, void* k_cache, void* v_cache, int max_len, const int64_t* pos,
+                        void* stream) {
+    if (!qkv || !cos || !sin || !q_out || !q_ostride || !k_cache || !v_cache || !pos || B < 1 || S < 1 || Hq < 1 || Hkv < 1 ||
+        D < 1 || cos_dim < 1 || cos_sb < 0 || cos_ss < 0 || max_len < 1)
+        return PBL_ERR_INVALID_ARG;
+    for (int j = 0; j < 3; ++j)
+        if (q_ostride[j] < 0) return PBL_ERR_INVALID_ARG;
+    const int64_t M = int64_t(B) * S;
+    const int64_t qend = int64_t(q_off) + int64_t(Hq) * D, kend = int64_t(k_off) + int64_t(Hkv) * D;
+    const int64_t vend = int64_t(v_off) + int64_t(Hkv) * D;
+    const int64_t xend = qend > kend ? (qend > vend ? qend : vend) : (kend > vend ? kend : vend);
+    if (xend > ld || M * (Hq + 2 * Hkv) * D > (int64_t(1) << 30) || int64_t(B) * Hkv * max_len * D > (int64_t(1) << 40))
+        return PBL_ERR_INVALID_ARG;
+    const size_t qb = size_t(((B - 1) * q_ostride[0] + int64_t(Hq - 1) * q_ostride[1] + (S - 1) * q_ostride[2] + D) * 2);
+    const size_t cacheb = size_t(int64_t(B) * Hkv * max_len * D * 2);
+    const size_t xb = size_t(((M - 1) * ld + xend) * 2);
+    const size_t cb = size_t(((B - 1) * cos_sb + (S - 1) * cos_ss + cos_dim) * 2);
+    const void* outs[3] = {q_out, k_cache, v_cache};
+    const size_t outb[3] = {qb, cacheb, cacheb};
+    for (int j = 0; j < 3; ++j) {
+        if (overlaps(outs[j], outb[j], qkv, xb) || overlaps(outs[j], outb[j], cos, cb) || overlaps(outs[j], outb[j], sin, cb) ||
+            overlaps(outs[j], outb[j], pos, 8))
+            return PBL_ERR_INVALID_ARG;
+        for (int o = j + 1; o < 3; ++o)
+            if (overlaps(outs[j], outb[j], outs[o], outb[o])) return PBL_ERR_INVALID_ARG;
+    }
+    if ((D != 64 && D != 128) || S > 4 || B > 4 || Hq % Hkv || cos_dim != D) return PBL_ERR_UNSUPPORTED;
+    RopeAppendArgs a{};
+    a.r.qkv = static_cast<const uint16_t*>(qkv);
+    a.r.cos = static_cast<const uint16_t*>(cos); a.r.sin = static_cast<const uint16_t*>(sin);
+    a.r.q_out = static_cast<uint16_t*>(q_out);
+    a.r.c_sb = cos_sb; a.r.c_ss = cos_ss;
+    a.r.q_ob = q_ostride[0]; a.r.q_oh = q_ostride[1]; a.r.q_os = q_ostride[2];
+    a.r.ld = ld; a.r.q_off = q_off; a.r.k_off = k_off;
+    a.r.S = S; a.r.Hq = Hq; a.r.H = Hq + 2 * Hkv; a.r.half = D / 2;
+    a.r.pairs = int(M * (Hq + 2 * Hkv) * (D / 2));
+    a.k_cache = static_cast<uint16_t*>(k_cache); a.v_cache = static_cast<uint16_t*>(v_cache);
+    a.pos = pos; a.v_off = v_off; a.Hkv = Hkv; a.max_len = max_len;
+    void* argv[] = {&a};
+    return hipLaunchKernel(reinterpret_cast<const void*>(pbl_rope_append_kernel), dim3((a.r.pairs + 255) / 256), dim3(256), argv, 0,
                            static_cast<hipStream_t>(stream)) == hipSuccess ? PBL_OK : PBL_ERR_LAUNCH;
 }
 

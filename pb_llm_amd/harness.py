@@ -343,6 +343,29 @@ class _FoldedMLP(nn.Module):
         return self.down_proj(self.act_fn(self.gate_proj(x)) * self.up_proj(x))
 
 
+# The HIP decode attention in folded layers (_folded_layer_forward) over a DecodeCache.  False: those layers append to the cache and
+# attend through HF's StaticLayer.update and attention interface instead (tools/bench_generate.py compares the two).
+DECODE_ATTENTION = True
+_DECODE_CACHE = None                     # the DecodeCache class, made on first use (transformers is imported lazily)
+
+
+def _decode_cache_layer(cache, layer_idx: int, batch: int, n_kv: int, head_dim: int):
+    """the StaticLayer of `cache` that the decode-attention branch may append to and attend over: cache is a DecodeCache, its layer
+    is a plain, initialised StaticLayer of fp16 [batch, n_kv, max_len, head_dim] tensors -- else None (HF's path)"""
+    if not DECODE_ATTENTION or _DECODE_CACHE is None or not isinstance(cache, _DECODE_CACHE) or layer_idx is None \
+            or layer_idx >= len(cache.layers):
+        return None
+    from transformers.cache_utils import StaticLayer
+    from .runtime import decode_attention_ok
+    lay = cache.layers[layer_idx]
+    if type(lay) is not StaticLayer or not lay.is_initialized or lay.keys.dtype != torch.float16:
+        return None
+    B, H, L, D = lay.keys.shape
+    if (B, H, D) != (batch, n_kv, head_dim) or not decode_attention_ok(batch, 1, n_kv, n_kv, head_dim, L):
+        return None
+    return lay
+
+
 def _folded_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
                           position_embeddings=None, **kwargs):
     """LlamaDecoderLayer.forward of a layer folded by fuse_decode_(epilogues=True), installed on the instance.  At <= 4 fp16 rows
@@ -367,17 +390,31 @@ def _folded_layer_forward(self, hidden_states, attention_mask=None, position_ids
         return y[:, a:b].reshape(B, S, b - a).view(B, S, -1, D).transpose(1, 2)
 
     cos, sin = position_embeddings
-    qk = rope_f16(y, o_q, o_k, B, S, (o_k - o_q) // D, (o_v - o_k) // D, D, cos, sin)
-    if qk is None:
-        qk = ML.apply_rotary_pos_emb(heads(o_q, o_k), heads(o_k, o_v), cos, sin)
-    q, k = qk
-    v = heads(o_v, o_end)
-    if past_key_values is not None:
-        k, v = past_key_values.update(k, v, attn.layer_idx)
-    interface = ML.ALL_ATTENTION_FUNCTIONS.get_interface(attn.config._attn_implementation, ML.eager_attention_forward)
-    a, _ = interface(attn, q, k, v, attention_mask, dropout=0.0 if not attn.training else attn.attention_dropout,
-                     scaling=attn.scaling, position_ids=position_ids, use_cache=use_cache, **kwargs)
-    a = a.reshape(B, S, -1).contiguous()
+    n_q, n_kv = (o_k - o_q) // D, (o_v - o_k) // D
+    a = None
+    lay = _decode_cache_layer(past_key_values, attn.layer_idx, B, n_kv, D)
+    if lay is not None and not attn.training:
+        # DecodeSession's cache: RoPE + the cache append in one launch, then the HIP decode attention over the valid rows only; it
+        # advances the layer's position on the device (StaticLayer.cumulative_length), as StaticLayer.update would have
+        from .runtime import decode_attention_f16, rope_append_f16
+        q = rope_append_f16(y, o_q, o_k, o_v, B, S, n_q, n_kv, D, cos, sin, lay.keys, lay.values, lay.cumulative_length)
+        if q is not None:
+            a = decode_attention_f16(q, lay.keys, lay.values, lay.cumulative_length, attn.scaling)
+            if a is None:                   # (decode_attention_ok held for rope_append_f16: the row is appended, the position not)
+                raise RuntimeError("decode_attention_f16 declined a shape rope_append_f16 took")
+            a = a.view(B, S, -1)
+    if a is None:
+        qk = rope_f16(y, o_q, o_k, B, S, n_q, n_kv, D, cos, sin)
+        if qk is None:
+            qk = ML.apply_rotary_pos_emb(heads(o_q, o_k), heads(o_k, o_v), cos, sin)
+        q, k = qk
+        v = heads(o_v, o_end)
+        if past_key_values is not None:
+            k, v = past_key_values.update(k, v, attn.layer_idx)
+        interface = ML.ALL_ATTENTION_FUNCTIONS.get_interface(attn.config._attn_implementation, ML.eager_attention_forward)
+        a, _ = interface(attn, q, k, v, attention_mask, dropout=0.0 if not attn.training else attn.attention_dropout,
+                         scaling=attn.scaling, position_ids=position_ids, use_cache=use_cache, **kwargs)
+        a = a.reshape(B, S, -1).contiguous()
     h1 = attn.o_proj.forward_residual(a, hidden_states)
     if h1 is None:
         h1 = hidden_states + attn.o_proj(a)
@@ -579,6 +616,195 @@ class GraphedForward:
         self.static_ids.copy_(ids)
         self.graph.replay()
         return self.static_logits
+
+
+def _decode_cache_class():
+    global _DECODE_CACHE
+    if _DECODE_CACHE is None:
+        from transformers.cache_utils import StaticCache
+
+        class DecodeCache(StaticCache):
+            """transformers' StaticCache for an UNPADDED batch whose rows all share one position, allocated up front (so that a
+            decode step can be captured before any row is written).  Made by DecodeSession / generate, not by the user.  HF code
+            that receives it treats it as a StaticCache: StaticLayer.update, prefill of more than 4 rows, unfolded layers and bf16
+            models keep working.  A folded layer (fuse_decode_(epilogues=True)) whose cache layer is a plain fp16 StaticLayer
+            appends to it and attends over its valid rows with the HIP decode attention (runtime.rope_append_f16 /
+            decode_attention_f16) instead; that path ignores the attention mask, hence the unpadded-batch contract."""
+
+            def __init__(self, config, batch: int, max_cache_len: int, device, dtype):
+                super().__init__(config=config, max_cache_len=max_cache_len)
+                text = config.get_text_config(decoder=True)
+                head_dim = getattr(text, "head_dim", None) or text.hidden_size // text.num_attention_heads
+                self.early_initialization(batch, text.num_key_value_heads, head_dim, dtype, torch.device(device))
+                self.batch = batch
+
+        DecodeCache.__qualname__ = "DecodeCache"
+        _DECODE_CACHE = DecodeCache
+    return _DECODE_CACHE
+
+
+def __getattr__(name):
+    if name == "DecodeCache":
+        return _decode_cache_class()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+class DecodeSession:
+    """Greedy-decoding state of `model` (a HF causal LM) for `batch` unpadded rows and at most `max_length` positions: a DecodeCache
+    on the device and, with graph=True, ONE decode step captured in a hipGraph on its first call and replayed for every later
+    token.  Every forward gets a ready 4D causal mask built on the device from the cache's position (create_causal_mask passes a
+    4D mask through), so nothing in a step reads the position on the host.  The host keeps its own count (`pos`) to enforce
+    max_length."""
+
+    def __init__(self, model: nn.Module, batch: int, max_length: int, graph: bool = True):
+        if batch < 1 or max_length < 1:
+            raise ValueError("DecodeSession: batch and max_length must be >= 1")
+        emb = model.get_input_embeddings().weight
+        self.model, self.batch, self.max_length, self.use_graph = model, int(batch), int(max_length), graph
+        self.device, self.dtype = emb.device, emb.dtype
+        self.cache = _decode_cache_class()(model.config, self.batch, self.max_length, self.device, self.dtype)
+        self._cols = torch.arange(self.max_length, device=self.device)
+        self._bool_mask = model.config._attn_implementation == "sdpa"
+        self.static_ids = torch.zeros(self.batch, 1, dtype=torch.long, device=self.device)
+        self.graph, self.static_logits, self.pos = None, None, 0
+
+    def _mask(self, seq: int) -> torch.Tensor:
+        """[batch, 1, seq, max_length]: query row s sees cache rows [0, position + s] (bool for SDPA, additive otherwise)"""
+        rows = self.cache.layers[0].cumulative_length + torch.arange(seq, device=self.device)
+        m = (self._cols[None, :] <= rows[:, None])[None, None].expand(self.batch, 1, seq, self.max_length)
+        if self._bool_mask:
+            return m
+        return torch.zeros((), dtype=self.dtype, device=self.device).masked_fill(~m, torch.finfo(self.dtype).min)
+
+    def _forward(self, ids: torch.Tensor) -> torch.Tensor:
+        out = self.model(ids, attention_mask=self._mask(ids.shape[1]), past_key_values=self.cache, use_cache=True, logits_to_keep=1)
+        return out.logits[:, -1]
+
+    def _advance(self, seq: int):
+        if self.pos + seq > self.max_length:
+            raise ValueError(f"DecodeSession: {self.pos} + {seq} positions exceed max_length = {self.max_length}")
+        self.pos += seq
+
+    @torch.no_grad()
+    def prefill(self, ids: torch.Tensor) -> torch.Tensor:
+        """ids [batch, S] at the current position, eagerly (<= 4 rows in folded layers: the HIP kernels; more: HF's StaticLayer.update
+        and attention).  Returns the last position's logits [batch, vocab]."""
+        if ids.dim() != 2 or ids.shape[0] != self.batch or ids.shape[1] < 1:
+            raise ValueError(f"DecodeSession.prefill: ids must be [{self.batch}, S >= 1]")
+        self._advance(ids.shape[1])
+        return self._forward(ids.to(self.device))
+
+    @torch.no_grad()
+    def step(self, tok: torch.Tensor) -> torch.Tensor:
+        """one token per row (tok [batch] or [batch, 1]) at the current position; returns the logits [batch, vocab] -- with
+        graph=True a view of the graph's static output, overwritten by the next step"""
+        if tok.numel() != self.batch:
+            raise ValueError(f"DecodeSession.step: one token per row ({self.batch})")
+        self._advance(1)
+        if not self.use_graph:
+            return self._forward(tok.reshape(self.batch, 1).to(self.device))
+        self.static_ids.copy_(tok.reshape(self.batch, 1))
+        if self.graph is None:
+            self._capture()
+        self.graph.replay()
+        return self.static_logits
+
+    def _capture(self):
+        """GraphedForward's pattern: warm-up on a side stream (it writes this position's rows, which the replay rewrites, and its
+        position advance is undone), then the capture, which runs nothing"""
+        lens = [lay.cumulative_length for lay in self.cache.layers]
+        saved = [t.clone() for t in lens]
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._forward(self.static_ids)
+                for t, v in zip(lens, saved):
+                    t.copy_(v)
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        torch.cuda.synchronize(self.device)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.static_logits = self._forward(self.static_ids)
+
+    def reset(self):
+        """zero the cache rows and positions (the captured step stays valid: same tensors)"""
+        self.cache.reset()
+        self.pos = 0
+
+
+def _generation_limits(model: nn.Module, prompt_len: int, max_length=None, max_new_tokens=None, eos_token_id=None,
+                       pad_token_id=None) -> tuple[int, list, int | None]:
+    """(total length, eos ids, pad id) as model.generate resolves them for greedy decoding: max_new_tokens wins over max_length;
+    without either, the generation config's max_new_tokens, else its max_length NEW tokens (capped at max_position_embeddings);
+    ValueError where nothing is left to generate.  eos defaults to the generation config's, pad to its pad_token_id, else the
+    first eos id"""
+    gc = getattr(model, "generation_config", None)
+    if max_new_tokens is None and max_length is None:
+        max_new_tokens = getattr(gc, "max_new_tokens", None)
+    if max_new_tokens is not None:
+        if int(max_new_tokens) < 1:
+            raise ValueError("generate: max_new_tokens must be >= 1")
+        total = prompt_len + int(max_new_tokens)
+    elif max_length is not None:
+        total = int(max_length)
+    else:                                          # the config's max_length counts NEW tokens then, within max_position_embeddings
+        total = prompt_len + int(getattr(gc, "max_length", None) or 20)
+        cap = getattr(getattr(model, "config", None), "max_position_embeddings", None)
+        total = min(total, cap) if cap is not None else total
+    if total <= prompt_len:
+        raise ValueError(f"Input length of input_ids is {prompt_len}, but `max_length` is set to {total}: set max_new_tokens")
+    if eos_token_id is None:
+        eos_token_id = getattr(gc, "eos_token_id", None)
+    eos = [] if eos_token_id is None else [int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])]
+    if pad_token_id is None:
+        pad_token_id = getattr(gc, "pad_token_id", None)
+    if pad_token_id is None and eos:
+        pad_token_id = eos[0]
+    return total, eos, None if pad_token_id is None else int(pad_token_id)
+
+
+_GREEDY_DEFAULTS = {"do_sample": False, "num_beams": 1, "use_cache": True}
+
+
+@torch.no_grad()
+def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None = None, max_new_tokens: int | None = None,
+             eos_token_id=None, pad_token_id: int | None = None, attention_mask: torch.Tensor | None = None, graph: bool = True,
+             **kwargs) -> torch.Tensor:
+    """Greedy decoding of an unpadded batch input_ids [B, P] on the GPU: what model.generate(input_ids, do_sample=False, ...)
+    returns -- the prompt followed by the new tokens, rows that met eos padded with pad_token_id, stopping when every row has
+    finished or the length limit is reached.  One DecodeSession: the prompt is prefilled eagerly, then each token replays the
+    captured decode step; the only device-to-host read per token is the all-finished check (none without an eos id).  An
+    attention_mask with zeros (a padded batch), any other generation argument (sampling, beams, ...), or a model off the GPU is
+    handed to model.generate unchanged."""
+    greedy = all(kwargs[k] == v for k, v in _GREEDY_DEFAULTS.items() if k in kwargs) and not set(kwargs) - set(_GREEDY_DEFAULTS)
+    padded = attention_mask is not None and not bool(attention_mask.all())
+    if not greedy or padded or not input_ids.is_cuda or input_ids.dim() != 2:
+        hf = dict(kwargs)
+        for k, v in (("max_length", max_length), ("max_new_tokens", max_new_tokens), ("eos_token_id", eos_token_id),
+                     ("pad_token_id", pad_token_id), ("attention_mask", attention_mask)):
+            if v is not None:
+                hf[k] = v
+        return model.generate(input_ids, **hf)
+    B, P = input_ids.shape
+    total, eos, pad = _generation_limits(model, P, max_length, max_new_tokens, eos_token_id, pad_token_id)
+    sess = DecodeSession(model, B, total - 1, graph=graph)
+    logits = sess.prefill(input_ids)
+    out = [input_ids]
+    eos_t = torch.tensor(eos, dtype=input_ids.dtype, device=input_ids.device) if eos else None
+    unfinished = torch.ones(B, dtype=torch.bool, device=input_ids.device)
+    cur = P
+    while True:
+        nxt = logits.float().argmax(-1).to(input_ids.dtype)
+        if eos_t is not None:
+            nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
+            unfinished &= ~torch.isin(nxt, eos_t)
+        out.append(nxt[:, None])
+        cur += 1
+        if cur >= total or (eos_t is not None and not bool(unfinished.any())):
+            break
+        logits = sess.step(nxt)
+    return torch.cat(out, 1)
 
 
 @torch.no_grad()

@@ -210,3 +210,81 @@ def rope_f16(qkv: torch.Tensor, q_off: int, k_off: int, batch: int, seq: int, n_
         return None
     _lib.check(rc, "rope")
     return q, k
+
+
+def _cache_args(k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, device, what: str):
+    """(B, Hkv, max_len, D) of a layer's static KV cache, after checking its form: [B, Hkv, max_len, D] fp16 contiguous k / v on
+    `device` and a one-element int64 position there (HF StaticLayer.keys / .values / .cumulative_length)"""
+    if k_cache.dtype != torch.float16 or v_cache.dtype != torch.float16 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape \
+            or not k_cache.is_contiguous() or not v_cache.is_contiguous() or k_cache.device != device or v_cache.device != device:
+        raise ValueError(f"{what}: k_cache / v_cache must be contiguous fp16 [B, Hkv, max_len, D] tensors on the activations' device")
+    if pos.dtype != torch.int64 or pos.numel() != 1 or pos.device != device:
+        raise ValueError(f"{what}: pos must be a one-element int64 tensor on the activations' device")
+    return tuple(int(d) for d in k_cache.shape)
+
+
+def decode_attention_ok(batch: int, seq: int, n_q: int, n_kv: int, head_dim: int, max_len: int) -> bool:
+    """the scope of rope_append_f16 + decode_attention_f16: where both entries run (the caller checks BEFORE the first of them, so
+    that a cache row is never appended without the attention that advances the position)"""
+    return head_dim in (64, 128) and 1 <= seq <= 4 and 1 <= batch <= 4 and n_kv >= 1 and n_q % n_kv == 0 and 1 <= max_len <= 65536
+
+
+def rope_append_f16(qkv: torch.Tensor, q_off: int, k_off: int, v_off: int, batch: int, seq: int, n_q: int, n_kv: int, head_dim: int,
+                    cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                    pos: torch.Tensor) -> torch.Tensor | None:
+    """rope_f16's q (same values, shape and strides), and in the same launch (pbl_rope_append_f16) the rotated k heads and the raw v
+    heads (n_kv heads from column v_off of qkv) written into rows [pos, pos + seq) of the layer's static cache k_cache / v_cache
+    [batch, n_kv, max_len, head_dim] fp16; pos (int64, on the device, read there) is not changed.  None where the entry declines
+    (head_dim not 64 / 128, seq > 4, batch > 4, n_q % n_kv) or cos / sin are not of rope_f16's form."""
+    if qkv.dim() != 2 or qkv.dtype != torch.float16 or not qkv.is_cuda or qkv.stride(1) != 1 or qkv.shape[0] != batch * seq:
+        raise ValueError("rope_append_f16: qkv must be an fp16 [batch * seq, n] GPU tensor with unit column stride")
+    if min(q_off, k_off, v_off) < 0 or max(q_off + n_q * head_dim, k_off + n_kv * head_dim, v_off + n_kv * head_dim) > qkv.shape[1]:
+        raise ValueError("rope_append_f16: the q / k / v heads must lie inside a row of qkv")
+    B, Hkv, max_len, D = _cache_args(k_cache, v_cache, pos, qkv.device, "rope_append_f16")
+    if (B, Hkv, D) != (batch, n_kv, head_dim):
+        raise ValueError("rope_append_f16: the cache is not [batch, n_kv, max_len, head_dim]")
+    if cos.dtype != torch.float16 or sin.dtype != torch.float16 or cos.device != qkv.device or sin.device != qkv.device \
+            or cos.dim() != 3 or cos.shape != sin.shape or cos.stride() != sin.stride() or cos.stride(-1) != 1 \
+            or cos.shape[0] not in (1, batch) or cos.shape[1] not in (1, seq) or cos.shape[-1] != head_dim \
+            or not decode_attention_ok(batch, seq, n_q, n_kv, head_dim, max_len):
+        return None
+    (qs, qst), _ = _rope_layout(qkv, q_off, k_off, batch, seq, n_q, n_kv, head_dim, cos, sin)
+    if qst[3] != 1 or qs != (batch, n_q, seq, head_dim):
+        return None
+    q = torch.empty_strided(qs, qst, dtype=torch.float16, device=qkv.device)
+    ld = qkv.stride(0) if qkv.shape[0] > 1 else qkv.shape[1]
+    rc = _lib.lib().pbl_rope_append_f16(qkv.data_ptr(), ld, q_off, k_off, v_off, batch, seq, n_q, n_kv, head_dim,
+                                        cos.data_ptr(), sin.data_ptr(), head_dim,
+                                        cos.stride(0) if cos.shape[0] > 1 else 0, cos.stride(1) if cos.shape[1] > 1 else 0,
+                                        q.data_ptr(), (C.c_int64 * 3)(*qst[:3]), k_cache.data_ptr(), v_cache.data_ptr(), max_len,
+                                        pos.data_ptr(), torch.cuda.current_stream(qkv.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "rope + cache append")
+    return q
+
+
+def decode_attention_f16(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor,
+                         scaling: float) -> torch.Tensor | None:
+    """softmax(scaling q k^T) v of a decode step over a static KV cache (pbl_decode_attn_f16): q [B, Hq, S, D] fp16 (unit d stride:
+    rope_append_f16's q), k_cache / v_cache [B, Hkv, max_len, D] fp16, pos the int64 device position -- query row s attends to
+    cache rows [0, pos + s].  Returns [B * S, Hq * D] fp16 (what LlamaAttention hands o_proj) and advances pos by S on the device.
+    None where the entry declines (decode_attention_ok)."""
+    if q.dim() != 4 or q.dtype != torch.float16 or not q.is_cuda or q.stride(3) != 1 or min(q.stride()) < 0:
+        raise ValueError("decode_attention_f16: q must be an fp16 [B, Hq, S, D] GPU tensor with unit d stride")
+    B, Hq, S, D = (int(d) for d in q.shape)
+    Bc, Hkv, max_len, Dc = _cache_args(k_cache, v_cache, pos, q.device, "decode_attention_f16")
+    if (Bc, Dc) != (B, D):
+        raise ValueError("decode_attention_f16: the cache is not [B, Hkv, max_len, D] for q [B, Hq, S, D]")
+    if not decode_attention_ok(B, S, Hq, Hkv, D, max_len):
+        return None
+    L = _lib.lib()
+    out = torch.empty(B * S, Hq * D, dtype=torch.float16, device=q.device)
+    ws = torch.empty(int(L.pbl_decode_attn_workspace_bytes(B, S, Hq, D, max_len)), dtype=torch.uint8, device=q.device)
+    rc = L.pbl_decode_attn_f16(q.data_ptr(), (C.c_int64 * 3)(*q.stride()[:3]), k_cache.data_ptr(), v_cache.data_ptr(), B, S, Hq, Hkv,
+                               D, max_len, float(scaling), pos.data_ptr(), out.data_ptr(), Hq * D, ws.data_ptr(), ws.numel(),
+                               torch.cuda.current_stream(q.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "decode attention")
+    return out
