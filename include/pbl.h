@@ -535,6 +535,36 @@ int pbl_decode_attn_f16(const void* q, const int64_t* q_stride, const void* k_ca
                         int Hkv, int D, int max_len, float scaling, int64_t* pos, void* out, uint32_t ldo, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* Token selection of a decode step (csrc/pbl_select.hip; harness.DecodeSession / harness.generate): temperature, top-k, top-p, the
+ * draw and the eos / pad bookkeeping of a generation loop in one launch per step (B > 1: a second, one-wave launch that counts the
+ * unfinished rows and advances the step).
+ *   logits [B, V] fp16, row b at logits + b ld elements (ld >= V); u [n_steps, B] fp32 uniforms in [0, 1), or NULL for greedy;
+ *   step, a DEVICE int64: row `step` of u and column col0 + step of tokens are used, then *step advances by one, so one captured
+ *   graph serves every step.  Per row, on VALUES (no sort order enters):
+ *     1. s_i = float(logit_i) / temperature in fp32;
+ *     2. top_k > 0: keep s_i >= the top_k-th largest s (every tie of that value stays; top_k >= V or 0: off);
+ *     3. top_p < 1: over the tokens kept so far, M(v) = the total weight of those with s_j <= v; every token of value v is removed
+ *        iff M(v) <= (1 - top_p) W and v is not the maximum (HF's TopPLogitsWarper, except that a block of tied values at the
+ *        boundary stays whole);
+ *     4. w_i = exp(s_i - max s) for kept tokens, W their sum: the token is the lowest index i, in vocabulary order, with
+ *        w_0 + ... + w_i > u W.  The weights are held as integers floor(2^44 w_i), so every sum is exact and order-free: the same
+ *        logits, u and parameters give the same token on every run (bit-stable, eager or replayed);
+ *     5. greedy (u NULL): the lowest index among the maxima; -0 equals +0 and a NaN counts as the maximum, as in torch.argmax.
+ *   Bookkeeping: a row whose unfinished[b] (one byte per row) is 0 gets `pad`; a row whose token is one of eos[0 .. n_eos) clears
+ *   its flag; the token goes to tokens[b * total + col0 + step] (int64 [B, total]) and to next_ids[b] (int64 [B]: the next step's
+ *   input); *n_unfinished (int32) = the rows still unfinished.  *status (int32, only ever OR-ed into): bit 0 = a row of a sampling
+ *   call held NaN or +inf or nothing finite (torch.multinomial would raise; the row falls back to rule 5), bit 1 = step outside
+ *   [0, n_steps) or col0 + step outside [0, total) (nothing is written to tokens then).  kept (may be NULL): [B, V] bytes, 1 where
+ *   the token survived the filters (greedy: the token alone) -- for tests.
+ * PBL_ERR_INVALID_ARG for NULL pointers (u, eos with n_eos = 0 and kept may be NULL), sizes < 1, ld < V, col0 outside [0, total),
+ * temperature <= 0, top_p outside (0, 1], top_k < 0 and outputs overlapping inputs or each other, before any device work;
+ * PBL_ERR_UNSUPPORTED for V > 524288.  No workspace, no allocation, no synchronisation, nothing read on the host: capturable in a
+ * hipGraph. */
+int pbl_select_token_f16(const void* logits, int64_t ld, int B, int V, float temperature, int top_k, float top_p, const float* u,
+                         int64_t n_steps, int64_t* step, const int64_t* eos, int n_eos, int64_t pad, uint8_t* unfinished,
+                         int64_t* tokens, int64_t total, int64_t col0, int64_t* next_ids, int32_t* n_unfinished, int32_t* status,
+                         uint8_t* kept, void* stream);
+
 /* ---------------- QAT step, weight side ------------------------------------------ */
 /* The elementwise work of one training step of BinaryXnorExceptOutliersLinear
  * (quant/outlier_quantizer.py:83-99; straight-through estimator quant/quantizer.py:18-25), fused into

@@ -650,11 +650,16 @@ def __getattr__(name):
 
 
 class DecodeSession:
-    """Greedy-decoding state of `model` (a HF causal LM) for `batch` unpadded rows and at most `max_length` positions: a DecodeCache
+    """Decoding state of `model` (a HF causal LM) for `batch` unpadded rows and at most `max_length` positions: a DecodeCache
     on the device and, with graph=True, ONE decode step captured in a hipGraph on its first call and replayed for every later
     token.  Every forward gets a ready 4D causal mask built on the device from the cache's position (create_causal_mask passes a
     4D mask through), so nothing in a step reads the position on the host.  The host keeps its own count (`pos`) to enforce
-    max_length."""
+    max_length.
+
+    prefill / step hand the logits back and leave the choice of the token to the caller.  begin_selection / select / step_select
+    keep the choice on the device as well (runtime.select_token_f16: greedy or temperature / top-k / top-p sampling, eos / pad
+    bookkeeping): the captured unit is then "forward over static_ids, select into static_ids", and a generation is one replay per
+    token with nothing read on the host (run_selection reads the unfinished count every poll_every tokens)."""
 
     def __init__(self, model: nn.Module, batch: int, max_length: int, graph: bool = True):
         if batch < 1 or max_length < 1:
@@ -667,6 +672,7 @@ class DecodeSession:
         self._bool_mask = model.config._attn_implementation == "sdpa"
         self.static_ids = torch.zeros(self.batch, 1, dtype=torch.long, device=self.device)
         self.graph, self.static_logits, self.pos = None, None, 0
+        self.sel, self.sel_graph = None, None
 
     def _mask(self, seq: int) -> torch.Tensor:
         """[batch, 1, seq, max_length]: query row s sees cache rows [0, position + s] (bool for SDPA, additive otherwise)"""
@@ -705,27 +711,109 @@ class DecodeSession:
             return self._forward(tok.reshape(self.batch, 1).to(self.device))
         self.static_ids.copy_(tok.reshape(self.batch, 1))
         if self.graph is None:
-            self._capture()
+            self.graph, self.static_logits = self._capture(lambda: self._forward(self.static_ids))
         self.graph.replay()
         return self.static_logits
 
-    def _capture(self):
-        """GraphedForward's pattern: warm-up on a side stream (it writes this position's rows, which the replay rewrites, and its
-        position advance is undone), then the capture, which runs nothing"""
-        lens = [lay.cumulative_length for lay in self.cache.layers]
-        saved = [t.clone() for t in lens]
+    def _capture(self, unit, state=()):
+        """GraphedForward's pattern: warm-up of `unit` on a side stream (it writes this position's rows, which the replay rewrites;
+        its position advance and what it did to the tensors in `state` are undone), then the capture, which runs nothing.
+        Returns (graph, what unit returned under capture)"""
+        keep = [lay.cumulative_length for lay in self.cache.layers] + list(state)
+        saved = [t.clone() for t in keep]
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             for _ in range(2):
-                self._forward(self.static_ids)
-                for t, v in zip(lens, saved):
+                unit()
+                for t, v in zip(keep, saved):
                     t.copy_(v)
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.static_logits = self._forward(self.static_ids)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = unit()
+        return graph, out
+
+    # ---- token selection on the device
+    def begin_selection(self, prompt: torch.Tensor, total: int, eos=(), pad: int | None = None, uniforms: torch.Tensor | None = None,
+                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+        """Start a generation whose tokens are chosen on the device: allocates the result `tokens` [batch, total] (int64, the
+        prompt [batch, P] in front, returned), the step counter, the rows' unfinished flags, their count and the status word.
+        uniforms None: greedy; else fp32 [>= total - P, batch] uniforms in [0, 1), row t for the t-th new token, with temperature /
+        top_k (0 = off) / top_p (1 = off).  eos: ids that finish a row (finished rows receive `pad`)."""
+        if prompt.dim() != 2 or prompt.shape[0] != self.batch or not prompt.shape[1] < total:
+            raise ValueError(f"DecodeSession.begin_selection: prompt must be [{self.batch}, P < total]")
+        dev, P = self.device, int(prompt.shape[1])
+        if uniforms is not None:
+            if uniforms.dim() != 2 or uniforms.shape[0] < total - P or uniforms.shape[1] != self.batch:
+                raise ValueError(f"DecodeSession.begin_selection: uniforms must be [>= {total - P}, {self.batch}]")
+            uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+        tokens = torch.zeros(self.batch, total, dtype=torch.long, device=dev)
+        tokens[:, :P] = prompt
+        eos = [int(e) for e in eos]
+        self.sel = dict(tokens=tokens, col0=P, n=int(total) - P, done=0, uniforms=uniforms, pad=0 if pad is None else int(pad),
+                        eos=torch.tensor(eos, dtype=torch.long, device=dev) if eos else None,
+                        step=torch.zeros(1, dtype=torch.long, device=dev), unfinished=torch.ones(self.batch, dtype=torch.bool, device=dev),
+                        count=torch.full((1,), self.batch, dtype=torch.int32, device=dev),
+                        status=torch.zeros(1, dtype=torch.int32, device=dev), params=(float(temperature), int(top_k), float(top_p)))
+        self.sel_graph = None                                  # a captured unit holds the previous selection's tensors and parameters
+        return tokens
+
+    @torch.no_grad()
+    def select(self, logits: torch.Tensor) -> None:
+        """choose the next token of every row from `logits` [batch, vocab] fp16 on the device: it lands in the result, in static_ids
+        (the next step's input) and in the bookkeeping of begin_selection.  A missing kernel is an error, not a fallback."""
+        from .runtime import select_token_f16
+        c = self.sel
+        T, k, p = c["params"]
+        if select_token_f16(logits, c["step"], c["unfinished"], c["tokens"], c["col0"], self.static_ids, c["count"], c["status"],
+                            temperature=T, top_k=k, top_p=p, uniforms=c["uniforms"], eos=c["eos"], pad=c["pad"]) is None:
+            raise ValueError("DecodeSession.select: pbl_select_token_f16 declines these logits (runtime.select_token_ok)")
+
+    def _unit(self):
+        self.select(self._forward(self.static_ids))
+
+    @torch.no_grad()
+    def step_select(self) -> None:
+        """one decode step over the tokens the last selection left in static_ids, and the selection of the next ones: with
+        graph=True ONE replay of a unit captured on the first call"""
+        self._advance(1)
+        if not self.use_graph:
+            return self._unit()
+        if self.sel_graph is None:
+            c = self.sel
+            self.sel_graph, _ = self._capture(self._unit, [self.static_ids, c["step"], c["unfinished"], c["count"], c["status"], c["tokens"]])
+        self.sel_graph.replay()
+
+    @torch.no_grad()
+    def run_selection(self, n: int, poll_every: int = 8) -> int:
+        """up to n more step_select calls; with eos ids, the device's count of unfinished rows is read after every poll_every-th new
+        token of the generation and the loop ends once it is zero (rows that had finished receive pad meanwhile).  Returns the
+        number of new tokens generated so far (the first one comes from select on the prefill's logits)."""
+        c = self.sel
+        for _ in range(n):
+            if c["eos"] is not None and c["done"] % poll_every == 0 and int(c["count"]) == 0:
+                break
+            self.step_select()
+            c["done"] += 1
+        return c["done"]
+
+    def selection_result(self) -> torch.Tensor:
+        """the prompt and the new tokens so far, cut after the column at which the last row finished (what a check after every
+        token would have returned); RuntimeError if a sampled row held NaN or +inf (torch.multinomial raises for such a row)"""
+        c = self.sel
+        status = int(c["status"])
+        if status & 1:
+            raise RuntimeError("generate: a row of logits held NaN or +inf (or nothing finite) while sampling")
+        if status & 2:
+            raise RuntimeError("generate: the selection step ran outside the result buffer or the table of uniforms")
+        P, done = c["col0"], c["done"]
+        if c["eos"] is not None and done:
+            hit = torch.isin(c["tokens"][:, P:P + done], c["eos"])
+            first = torch.where(hit.any(1), hit.int().argmax(1) + 1, done)
+            done = int(first.max())
+        return c["tokens"][:, :P + done]
 
     def reset(self):
         """zero the cache rows and positions (the captured step stays valid: same tensors)"""
@@ -765,31 +853,96 @@ def _generation_limits(model: nn.Module, prompt_len: int, max_length=None, max_n
 
 
 _GREEDY_DEFAULTS = {"do_sample": False, "num_beams": 1, "use_cache": True}
+_SAMPLING_ARGS = ("temperature", "top_k", "top_p")
+
+
+def _sampling_params(model: nn.Module, temperature=None, top_k=None, top_p=None) -> tuple[float, int, float]:
+    """(temperature, top_k, top_p) as model.generate resolves them for do_sample=True: the argument, else the value in
+    model.generation_config, else -- for fields still None -- transformers' GenerationConfig._get_default_generation_params().
+    temperature 1.0, top_k 0 and top_p 1.0 mean "off" (HF builds no warper for them)."""
+    from transformers import GenerationConfig
+    gc = getattr(model, "generation_config", None)
+    defaults = GenerationConfig._get_default_generation_params()
+    vals = []
+    for name, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p)):
+        if v is None:
+            v = getattr(gc, name, None)
+        if v is None:
+            v = defaults[name]
+        vals.append(v)
+    return float(vals[0]), int(vals[1]), float(vals[2])
 
 
 @torch.no_grad()
 def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None = None, max_new_tokens: int | None = None,
              eos_token_id=None, pad_token_id: int | None = None, attention_mask: torch.Tensor | None = None, graph: bool = True,
+             generator: torch.Generator | None = None, uniforms: torch.Tensor | None = None, poll_every: int = 8,
              **kwargs) -> torch.Tensor:
-    """Greedy decoding of an unpadded batch input_ids [B, P] on the GPU: what model.generate(input_ids, do_sample=False, ...)
-    returns -- the prompt followed by the new tokens, rows that met eos padded with pad_token_id, stopping when every row has
-    finished or the length limit is reached.  One DecodeSession: the prompt is prefilled eagerly, then each token replays the
-    captured decode step; the only device-to-host read per token is the all-finished check (none without an eos id).  An
-    attention_mask with zeros (a padded batch), any other generation argument (sampling, beams, ...), or a model off the GPU is
-    handed to model.generate unchanged."""
-    greedy = all(kwargs[k] == v for k, v in _GREEDY_DEFAULTS.items() if k in kwargs) and not set(kwargs) - set(_GREEDY_DEFAULTS)
+    """Decoding of an unpadded batch input_ids [B, P] on the GPU: greedy -- what model.generate(input_ids, do_sample=False, ...)
+    returns -- or, with do_sample=True, sampling with temperature / top_k / top_p (values not passed are resolved as model.generate
+    resolves them: _sampling_params).  The result is the prompt followed by the new tokens, rows that met eos padded with
+    pad_token_id, ending where every row has finished or at the length limit.  One DecodeSession: the prompt is prefilled eagerly,
+    then each token replays ONE captured unit -- the decode step and the HIP token selection (pbl_select_token_f16), which writes
+    the token into the result and into the next step's input and keeps the eos / pad bookkeeping on the device.  The host reads
+    the count of unfinished rows every `poll_every` tokens (never without an eos id); tokens generated after every row finished
+    are pad and are cut off, so the result does not depend on poll_every.
+
+    Sampling draws its uniforms ONCE per call, before the loop: torch.rand([new tokens, B]) from `generator` (default: the default
+    generator of the model's device, so torch.manual_seed(n) reproduces a run), or the caller's table `uniforms` [>= new tokens, B]
+    (values in [0, 1)).  graph=True and graph=False consume the same numbers and give the same tokens.  The token stream for a
+    given seed differs from model.generate's (torch.multinomial consumes the generator differently); the distribution is the same,
+    up to HF's arbitrary choice inside a block of tied values at the top-p boundary.
+
+    Handed to model.generate unchanged: an attention_mask with zeros (a padded batch), a model off the GPU, beams, any other
+    generation argument (repetition_penalty, min_p, ...), do_sample=False together with sampling arguments, and sampling on a model
+    whose logits are not fp16.  model.generate cannot honour `generator` or `uniforms`, so a call that passes one of them and must
+    be handed over raises ValueError.  Greedy decoding of logits that are not fp16 keeps the selection in torch."""
+    sample = kwargs.get("do_sample", False) is True
+    fixed = {k: v for k, v in _GREEDY_DEFAULTS.items() if not (sample and k == "do_sample")}
+    known = set(_GREEDY_DEFAULTS) | (set(_SAMPLING_ARGS) if sample else set())
+    native = all(kwargs[k] == v for k, v in fixed.items() if k in kwargs) and not set(kwargs) - known
     padded = attention_mask is not None and not bool(attention_mask.all())
-    if not greedy or padded or not input_ids.is_cuda or input_ids.dim() != 2:
+    if native and sample:
+        T, top_k, top_p = _sampling_params(model, *(kwargs.get(k) for k in _SAMPLING_ARGS))
+        native = T > 0 and top_k >= 0 and 0 < top_p <= 1 and model.get_input_embeddings().weight.dtype == torch.float16
+
+    def hand_over():
+        if generator is not None or uniforms is not None:
+            raise ValueError("generate: generator= and uniforms= belong to the sampling loop on the GPU (an unpadded batch on a GPU model "
+                             "with fp16 logits, do_sample=True with temperature / top_k / top_p only); model.generate cannot honour them")
         hf = dict(kwargs)
         for k, v in (("max_length", max_length), ("max_new_tokens", max_new_tokens), ("eos_token_id", eos_token_id),
                      ("pad_token_id", pad_token_id), ("attention_mask", attention_mask)):
             if v is not None:
                 hf[k] = v
         return model.generate(input_ids, **hf)
+
+    if not native or padded or not input_ids.is_cuda or input_ids.dim() != 2:
+        return hand_over()
+    if poll_every < 1:
+        raise ValueError("generate: poll_every must be >= 1")
     B, P = input_ids.shape
     total, eos, pad = _generation_limits(model, P, max_length, max_new_tokens, eos_token_id, pad_token_id)
+    from .runtime import select_token_ok
     sess = DecodeSession(model, B, total - 1, graph=graph)
     logits = sess.prefill(input_ids)
+    if logits.dtype == torch.float16 and select_token_ok(B, logits.shape[1]):
+        table = None
+        if sample:
+            if uniforms is not None:
+                table = uniforms
+            else:                                          # one draw for the whole call; a host generator draws on the host
+                gdev = generator.device if generator is not None else input_ids.device
+                table = torch.rand(total - P, B, generator=generator, device=gdev, dtype=torch.float32)
+        else:
+            T, top_k, top_p = 1.0, 0, 1.0
+        sess.begin_selection(input_ids, total, eos=eos, pad=pad, uniforms=table, temperature=T, top_k=top_k, top_p=top_p)
+        sess.select(logits)
+        sess.sel["done"] = 1
+        sess.run_selection(total - P - 1, poll_every)
+        return sess.selection_result()
+    if sample:
+        return hand_over()
     out = [input_ids]
     eos_t = torch.tensor(eos, dtype=input_ids.dtype, device=input_ids.device) if eos else None
     unfinished = torch.ones(B, dtype=torch.bool, device=input_ids.device)

@@ -288,3 +288,60 @@ def decode_attention_f16(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
         return None
     _lib.check(rc, "decode attention")
     return out
+
+
+SELECT_MAX_VOCAB = 1 << 19
+
+
+def select_token_ok(batch: int, vocab: int) -> bool:
+    """the scope of select_token_f16 (pbl_select_token_f16): any batch, a vocabulary of at most 2^19 words"""
+    return batch >= 1 and 1 <= vocab <= SELECT_MAX_VOCAB
+
+
+def select_token_f16(logits: torch.Tensor, step: torch.Tensor, unfinished: torch.Tensor, tokens: torch.Tensor, col0: int,
+                     next_ids: torch.Tensor, n_unfinished: torch.Tensor, status: torch.Tensor, temperature: float = 1.0,
+                     top_k: int = 0, top_p: float = 1.0, uniforms: torch.Tensor | None = None, eos: torch.Tensor | None = None,
+                     pad: int = 0, kept: torch.Tensor | None = None) -> bool | None:
+    """One token per row of logits [B, V] fp16 (unit column stride; the view out.logits[:, -1] is fine), chosen and booked on the
+    device in one call (pbl_select_token_f16; the rules are in include/pbl.h): greedy when `uniforms` is None, else temperature /
+    top_k (0 = off) / top_p (1 = off) sampling with the uniform uniforms[step, b] (fp32 [n_steps, B], values in [0, 1)).  All state
+    is on the logits' device: step (int64, one element; advanced by one), unfinished (bool or uint8 [B]), tokens (int64 [B, total];
+    column col0 + step receives the token), next_ids (int64, B elements: the next step's input), n_unfinished and status (int32,
+    one element each; status bit 0: a sampled row held NaN / +inf, bit 1: step out of range), eos (int64 ids or None), kept
+    (optional uint8 [B, V]: the mask of tokens that survived the filters).  Nothing is read on the host and nothing allocated:
+    capturable in a hipGraph.  True when it ran, None where the entry declines (select_token_ok)."""
+    def dev(t, dtypes, n=None):
+        return t.is_cuda and t.device == logits.device and t.dtype in dtypes and t.is_contiguous() and (n is None or t.numel() == n)
+
+    if not logits.is_cuda or logits.dim() != 2 or logits.dtype != torch.float16 or logits.stride(1) != 1 or logits.shape[1] < 1 \
+            or logits.shape[0] < 1 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        raise ValueError("select_token_f16: logits must be an fp16 [B, V] GPU tensor with unit column stride")
+    B, V = (int(d) for d in logits.shape)
+    flags = (torch.bool, torch.uint8)
+    if not (dev(step, (torch.int64,), 1) and dev(unfinished, flags, B) and dev(next_ids, (torch.int64,), B)
+            and dev(n_unfinished, (torch.int32,), 1) and dev(status, (torch.int32,), 1)):
+        raise ValueError("select_token_f16: step (int64), unfinished (bool [B]), next_ids (int64 [B]), n_unfinished and status (int32) "
+                         "must be contiguous tensors on the logits' device")
+    if not dev(tokens, (torch.int64,)) or tokens.dim() != 2 or tokens.shape[0] != B or not 0 <= col0 < tokens.shape[1]:
+        raise ValueError("select_token_f16: tokens must be a contiguous int64 [B, total] tensor on the logits' device, 0 <= col0 < total")
+    if uniforms is not None and (not dev(uniforms, (torch.float32,)) or uniforms.dim() != 2 or uniforms.shape[1] != B or uniforms.shape[0] < 1):
+        raise ValueError("select_token_f16: uniforms must be a contiguous fp32 [n_steps, B] tensor on the logits' device")
+    if eos is not None and (not dev(eos, (torch.int64,)) or eos.dim() != 1):
+        raise ValueError("select_token_f16: eos must be a 1-D int64 tensor on the logits' device")
+    if kept is not None and not dev(kept, flags, B * V):
+        raise ValueError("select_token_f16: kept must be a contiguous uint8 [B, V] tensor on the logits' device")
+    if not temperature > 0 or top_k < 0 or not 0 < top_p <= 1:
+        raise ValueError("select_token_f16: temperature > 0, top_k >= 0 and 0 < top_p <= 1")
+    if not select_token_ok(B, V):
+        return None
+    n_eos = 0 if eos is None else int(eos.numel())
+    rc = _lib.lib().pbl_select_token_f16(
+        logits.data_ptr(), logits.stride(0) if B > 1 else V, B, V, float(temperature), int(top_k), float(top_p),
+        None if uniforms is None else uniforms.data_ptr(), 0 if uniforms is None else int(uniforms.shape[0]), step.data_ptr(),
+        eos.data_ptr() if n_eos else None, n_eos, int(pad), unfinished.data_ptr(), tokens.data_ptr(), int(tokens.shape[1]), int(col0),
+        next_ids.data_ptr(), n_unfinished.data_ptr(), status.data_ptr(), None if kept is None else kept.data_ptr(),
+        torch.cuda.current_stream(logits.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "token selection")
+    return True
