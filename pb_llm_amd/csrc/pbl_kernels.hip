@@ -1478,6 +1478,15 @@ static Route route_of(const pbl_layer* layer, int M, bool x_aligned) {
     return r;
 }
 
+// what every entry that runs ONE GEMV pass of a group-free layer (one_pass) checks first: PBL_OK and the route, else the entry's
+// return code (a misaligned blob; column groups or more rows than one pass takes: PBL_ERR_UNSUPPORTED)
+static int one_pass_route(const pbl_layer* layer, int M, Route& r) {
+    if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
+    if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
+    r = route_of(layer, M, true);
+    return M > r.mb_max ? PBL_ERR_UNSUPPORTED : PBL_OK;
+}
+
 size_t pbl_linear_workspace_bytes(const pbl_layer* layer, int M) {
     if (!layer || M < 1) return 0;
     return route_of(layer, M, true).mfma ? pbl_mfma_workspace_bytes(layer, M < 32 ? M : 32) : 0;
@@ -1543,26 +1552,14 @@ int pbl_linear_f16_ws(const pbl_layer* layer, const void* x, void* y, int M, int
 // at most 4): PBL_ERR_UNSUPPORTED otherwise -- the caller then runs the three-launch form, which serves every kernel family.
 int pbl_linear_bf16(const pbl_layer* layer, const void* x_bf16, void* y, int M, int y_f32, void* stream) {
     if (!layer || !layer->blob || !x_bf16 || !y || M < 1) return PBL_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
-    if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
-    const Route r = route_of(layer, M, true);
-    if (M > r.mb_max) return PBL_ERR_UNSUPPORTED;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool sf = layer->flags & PBL_FLAG_SAL_F16;
+    Route r;
+    if (const int rc = one_pass_route(layer, M, r)) return rc;
     GemvArgs a{};
     a.layer = *layer;
     a.x = static_cast<const _Float16*>(x_bf16);                  // (bf16 bits: the XB instantiation reads them as such)
     a.y = y;
     a.M = M; a.y_f32 = y_f32; a.grouped = 0; a.x_bf16 = 1;
-    const int split = r.split, wpb = r.wpb;
-    const dim3 grid(split > 1 ? layer->NRB : (layer->NRB + wpb - 1) / wpb, 1, 1);
-    const size_t lds = lds_bytes(layer->P, layer->max_nch, M, wpb, split);
-    switch (split) {
-        case 8: return launch_split<8>(M, sf, a, grid, lds, st);
-        case 4: return launch_split<4>(M, sf, a, grid, lds, st);
-        case 2: return launch_split<2>(M, sf, a, grid, lds, st);
-        default: return wpb == 4 ? launch_mb<4>(M, sf, a, grid, lds, st) : launch_mb<1>(M, sf, a, grid, lds, st);
-    }
+    return one_pass<XP_NONE>(layer, r.split, r.wpb, a, M, stream);
 }
 
 // LLaMA's MLP tail in ONE launch: y [M, N] = down_proj(silu(gate) * up), the GEMV's staging phase building its x row from the fused
@@ -1573,27 +1570,15 @@ int pbl_linear_f16_swiglu(const pbl_layer* layer, const void* gate_up, uint32_t 
                           void* stream) {
     if (!layer || !layer->blob || !gate_up || !y || M < 1 || up_off < layer->K || uint64_t(ldx) < uint64_t(up_off) + layer->K)
         return PBL_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
-    if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
-    const Route r = route_of(layer, M, true);
-    if (M > r.mb_max) return PBL_ERR_UNSUPPORTED;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool sf = layer->flags & PBL_FLAG_SAL_F16;
+    Route r;
+    if (const int rc = one_pass_route(layer, M, r)) return rc;
     GemvArgs a{};
     a.layer = *layer;
     a.x = static_cast<const _Float16*>(gate_up);
     a.y = y;
     a.M = M; a.y_f32 = y_f32; a.grouped = 0;
     a.ldx = ldx; a.up_off = up_off;
-    const int split = r.split, wpb = r.wpb;
-    const dim3 grid(split > 1 ? layer->NRB : (layer->NRB + wpb - 1) / wpb, 1, 1);
-    const size_t lds = lds_bytes(layer->P, layer->max_nch, M, wpb, split);
-    switch (split) {
-        case 8: return launch_split<8, XP_SWIGLU>(M, sf, a, grid, lds, st);
-        case 4: return launch_split<4, XP_SWIGLU>(M, sf, a, grid, lds, st);
-        case 2: return launch_split<2, XP_SWIGLU>(M, sf, a, grid, lds, st);
-        default: return wpb == 4 ? launch_mb<4, XP_SWIGLU>(M, sf, a, grid, lds, st) : launch_mb<1, XP_SWIGLU>(M, sf, a, grid, lds, st);
-    }
+    return one_pass<XP_SWIGLU>(layer, r.split, r.wpb, a, M, stream);
 }
 
 // A decoder layer's residual adds in the GEMV's store (XE_RESIDUAL): y [M, N] fp16 = fp16(fp16(layer(x)) + residual), residual
@@ -1604,10 +1589,8 @@ int pbl_linear_f16_residual(const pbl_layer* layer, const void* x, const void* r
     const size_t ybytes = size_t(M) * layer->N * 2;
     if (overlaps(y, ybytes, x, size_t(M) * layer->K * 2) || overlaps(y, ybytes, residual, (size_t(M - 1) * ldr + layer->N) * 2))
         return PBL_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
-    if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
-    const Route r = route_of(layer, M, true);
-    if (M > r.mb_max) return PBL_ERR_UNSUPPORTED;
+    Route r;
+    if (const int rc = one_pass_route(layer, M, r)) return rc;
     GemvArgs a{};
     a.layer = *layer;
     a.x = static_cast<const _Float16*>(x);
@@ -1628,10 +1611,8 @@ int pbl_linear_f16_swiglu_residual(const pbl_layer* layer, const void* gate_up, 
     if (overlaps(y, ybytes, gate_up, (size_t(M - 1) * ldx + up_off + layer->K) * 2) ||
         overlaps(y, ybytes, residual, (size_t(M - 1) * ldr + layer->N) * 2))
         return PBL_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
-    if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
-    const Route r = route_of(layer, M, true);
-    if (M > r.mb_max) return PBL_ERR_UNSUPPORTED;
+    Route r;
+    if (const int rc = one_pass_route(layer, M, r)) return rc;
     GemvArgs a{};
     a.layer = *layer;
     a.x = static_cast<const _Float16*>(gate_up);

@@ -1,0 +1,382 @@
+"""Generation over a static KV cache (harness.py re-exports it): DecodeCache, DecodeSession and `generate`, model.generate's counterpart
+for an unpadded batch on the GPU.  Depends on runtime.py only; transformers is imported on first use."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+import torch.nn as nn
+
+from . import runtime
+
+# The HIP decode attention in folded layers (fusion._folded_layer_forward) over a DecodeCache.  False: those layers append to the
+# cache and attend through HF's StaticLayer.update and attention interface instead (tools/bench_generate.py compares the two).  Read
+# HERE when a step runs or is captured: nothing re-exports it.
+DECODE_ATTENTION = True
+_DECODE_CACHE = None                     # the DecodeCache class, made on first use (transformers is imported lazily)
+
+
+def _decode_cache_layer(cache, layer_idx: int, batch: int, n_kv: int, head_dim: int):
+    """the StaticLayer of `cache` that the decode-attention branch may append to and attend over: cache is a DecodeCache, its layer
+    is a plain, initialised StaticLayer of fp16 [batch, n_kv, max_len, head_dim] tensors -- else None (HF's path)"""
+    if not DECODE_ATTENTION or _DECODE_CACHE is None or not isinstance(cache, _DECODE_CACHE) or layer_idx is None \
+            or layer_idx >= len(cache.layers):
+        return None
+    from transformers.cache_utils import StaticLayer
+    lay = cache.layers[layer_idx]
+    if type(lay) is not StaticLayer or not lay.is_initialized or lay.keys.dtype != torch.float16:
+        return None
+    B, H, L, D = lay.keys.shape
+    if (B, H, D) != (batch, n_kv, head_dim) or not runtime.decode_attention_ok(batch, 1, n_kv, n_kv, head_dim, L):
+        return None
+    return lay
+
+
+def _decode_cache_class():
+    global _DECODE_CACHE
+    if _DECODE_CACHE is None:
+        from transformers.cache_utils import StaticCache
+
+        class DecodeCache(StaticCache):
+            """transformers' StaticCache for an UNPADDED batch whose rows all share one position, allocated up front (so that a
+            decode step can be captured before any row is written).  Made by DecodeSession / generate, not by the user.  HF code
+            that receives it treats it as a StaticCache: StaticLayer.update, prefill of more than 4 rows, unfolded layers and bf16
+            models keep working.  A folded layer (fuse_decode_(epilogues=True)) whose cache layer is a plain fp16 StaticLayer
+            appends to it and attends over its valid rows with the HIP decode attention (runtime.rope_append_f16 /
+            decode_attention_f16) instead; that path ignores the attention mask, hence the unpadded-batch contract."""
+
+            def __init__(self, config, batch: int, max_cache_len: int, device, dtype):
+                super().__init__(config=config, max_cache_len=max_cache_len)
+                text = config.get_text_config(decoder=True)
+                head_dim = getattr(text, "head_dim", None) or text.hidden_size // text.num_attention_heads
+                self.early_initialization(batch, text.num_key_value_heads, head_dim, dtype, torch.device(device))
+                self.batch = batch
+
+        DecodeCache.__qualname__ = "DecodeCache"
+        _DECODE_CACHE = DecodeCache
+    return _DECODE_CACHE
+
+
+def _capture_graph(unit, device, restore=(), warmup: int = 2):
+    """Warm `unit` up on a side stream (after every run the tensors in `restore` get their values back), then capture ONE run of it
+    in a hipGraph -- the capture runs nothing.  Returns (graph, what unit returned under capture)"""
+    saved = [t.clone() for t in restore]
+    s = torch.cuda.Stream(device)
+    s.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(s), torch.no_grad():
+        for _ in range(warmup):
+            unit()
+            for t, v in zip(restore, saved):
+                t.copy_(v)
+    torch.cuda.current_stream(device).wait_stream(s)
+    torch.cuda.synchronize(device)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph), torch.no_grad():
+        out = unit()
+    return graph, out
+
+
+@dataclass
+class _Selection:
+    """DecodeSession.begin_selection's state: prompt in columns [0, col0) of `tokens`, n tokens wanted, `done` so far; params (T, k, p)"""
+    tokens: torch.Tensor
+    col0: int
+    n: int
+    done: int
+    uniforms: torch.Tensor | None
+    pad: int
+    eos: torch.Tensor | None
+    step: torch.Tensor
+    unfinished: torch.Tensor
+    count: torch.Tensor
+    status: torch.Tensor
+    params: tuple[float, int, float]
+
+
+class DecodeSession:
+    """Decoding state of `model` (a HF causal LM) for `batch` unpadded rows and at most `max_length` positions: a DecodeCache
+    on the device and, with graph=True, ONE decode step captured in a hipGraph on its first call and replayed for every later
+    token.  Every forward gets a ready 4D causal mask built on the device from the cache's position (create_causal_mask passes a
+    4D mask through), so nothing in a step reads the position on the host.  The host keeps its own count (`pos`) to enforce
+    max_length.
+
+    prefill / step hand the logits back and leave the choice of the token to the caller.  begin_selection / select / step_select
+    keep the choice on the device as well (runtime.select_token_f16: greedy or temperature / top-k / top-p sampling, eos / pad
+    bookkeeping): the captured unit is then "forward over static_ids, select into static_ids", and a generation is one replay per
+    token with nothing read on the host (run_selection reads the unfinished count every poll_every tokens)."""
+
+    def __init__(self, model: nn.Module, batch: int, max_length: int, graph: bool = True):
+        if batch < 1 or max_length < 1:
+            raise ValueError("DecodeSession: batch and max_length must be >= 1")
+        emb = model.get_input_embeddings().weight
+        self.model, self.batch, self.max_length, self.use_graph = model, int(batch), int(max_length), graph
+        self.device, self.dtype = emb.device, emb.dtype
+        self.cache = _decode_cache_class()(model.config, self.batch, self.max_length, self.device, self.dtype)
+        self._cols = torch.arange(self.max_length, device=self.device)
+        self._bool_mask = model.config._attn_implementation == "sdpa"
+        self.static_ids = torch.zeros(self.batch, 1, dtype=torch.long, device=self.device)
+        self.graph, self.static_logits, self.sel, self.sel_graph, self.pos = None, None, None, None, 0
+
+    def _mask(self, seq: int) -> torch.Tensor:
+        """[batch, 1, seq, max_length]: query row s sees cache rows [0, position + s] (bool for SDPA, additive otherwise)"""
+        rows = self.cache.layers[0].cumulative_length + torch.arange(seq, device=self.device)
+        m = (self._cols[None, :] <= rows[:, None])[None, None].expand(self.batch, 1, seq, self.max_length)
+        if self._bool_mask:
+            return m
+        return torch.zeros((), dtype=self.dtype, device=self.device).masked_fill(~m, torch.finfo(self.dtype).min)
+
+    def _forward(self, ids: torch.Tensor) -> torch.Tensor:
+        out = self.model(ids, attention_mask=self._mask(ids.shape[1]), past_key_values=self.cache, use_cache=True, logits_to_keep=1)
+        return out.logits[:, -1]
+
+    def _advance(self, seq: int):
+        if self.pos + seq > self.max_length:
+            raise ValueError(f"DecodeSession: {self.pos} + {seq} positions exceed max_length = {self.max_length}")
+        self.pos += seq
+
+    @torch.no_grad()
+    def prefill(self, ids: torch.Tensor) -> torch.Tensor:
+        """ids [batch, S] at the current position, eagerly (<= 4 rows in folded layers: the HIP kernels; more: HF's StaticLayer.update
+        and attention).  Returns the last position's logits [batch, vocab]."""
+        if ids.dim() != 2 or ids.shape[0] != self.batch or ids.shape[1] < 1:
+            raise ValueError(f"DecodeSession.prefill: ids must be [{self.batch}, S >= 1]")
+        self._advance(ids.shape[1])
+        return self._forward(ids.to(self.device))
+
+    @torch.no_grad()
+    def step(self, tok: torch.Tensor) -> torch.Tensor:
+        """one token per row (tok [batch] or [batch, 1]) at the current position; returns the logits [batch, vocab] -- with
+        graph=True a view of the graph's static output, overwritten by the next step"""
+        if tok.numel() != self.batch:
+            raise ValueError(f"DecodeSession.step: one token per row ({self.batch})")
+        self._advance(1)
+        if not self.use_graph:
+            return self._forward(tok.reshape(self.batch, 1).to(self.device))
+        self.static_ids.copy_(tok.reshape(self.batch, 1))
+        if self.graph is None:
+            self.graph, self.static_logits = self._capture(lambda: self._forward(self.static_ids))
+        self.graph.replay()
+        return self.static_logits
+
+    def _capture(self, unit, state=()):
+        """_capture_graph of `unit`: its warm-up writes this position's rows, which the replay rewrites; its position advance and what
+        it did to the tensors in `state` are undone"""
+        return _capture_graph(unit, self.device, [lay.cumulative_length for lay in self.cache.layers] + list(state))
+
+    # ---- token selection on the device
+    def begin_selection(self, prompt: torch.Tensor, total: int, eos=(), pad: int | None = None, uniforms: torch.Tensor | None = None,
+                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+        """Start a generation whose tokens are chosen on the device: allocates the result `tokens` [batch, total] (int64, the
+        prompt [batch, P] in front, returned), the step counter, the rows' unfinished flags, their count and the status word.
+        uniforms None: greedy; else fp32 [>= total - P, batch] uniforms in [0, 1), row t for the t-th new token, with temperature /
+        top_k (0 = off) / top_p (1 = off).  eos: ids that finish a row (finished rows receive `pad`)."""
+        if prompt.dim() != 2 or prompt.shape[0] != self.batch or not prompt.shape[1] < total:
+            raise ValueError(f"DecodeSession.begin_selection: prompt must be [{self.batch}, P < total]")
+        dev, P = self.device, int(prompt.shape[1])
+        if uniforms is not None:
+            if uniforms.dim() != 2 or uniforms.shape[0] < total - P or uniforms.shape[1] != self.batch:
+                raise ValueError(f"DecodeSession.begin_selection: uniforms must be [>= {total - P}, {self.batch}]")
+            uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+        tokens = torch.zeros(self.batch, total, dtype=torch.long, device=dev)
+        tokens[:, :P] = prompt
+        eos = [int(e) for e in eos]
+        self.sel = _Selection(tokens=tokens, col0=P, n=int(total) - P, done=0, uniforms=uniforms, pad=0 if pad is None else int(pad),
+                              eos=torch.tensor(eos, dtype=torch.long, device=dev) if eos else None,
+                              step=torch.zeros(1, dtype=torch.long, device=dev), unfinished=torch.ones(self.batch, dtype=torch.bool, device=dev),
+                              count=torch.full((1,), self.batch, dtype=torch.int32, device=dev),
+                              status=torch.zeros(1, dtype=torch.int32, device=dev), params=(float(temperature), int(top_k), float(top_p)))
+        self.sel_graph = None                                  # a captured unit holds the previous selection's tensors and parameters
+        return tokens
+
+    @torch.no_grad()
+    def select(self, logits: torch.Tensor) -> None:
+        """choose the next token of every row from `logits` [batch, vocab] fp16 on the device: it lands in the result, in static_ids
+        (the next step's input) and in the bookkeeping of begin_selection.  A missing kernel is an error, not a fallback."""
+        c = self.sel
+        T, k, p = c.params
+        if runtime.select_token_f16(logits, c.step, c.unfinished, c.tokens, c.col0, self.static_ids, c.count, c.status,
+                                    temperature=T, top_k=k, top_p=p, uniforms=c.uniforms, eos=c.eos, pad=c.pad) is None:
+            raise ValueError("DecodeSession.select: pbl_select_token_f16 declines these logits (runtime.select_token_ok)")
+
+    def _unit(self):
+        self.select(self._forward(self.static_ids))
+
+    @torch.no_grad()
+    def step_select(self) -> None:
+        """one decode step over the tokens the last selection left in static_ids, and the selection of the next ones: with
+        graph=True ONE replay of a unit captured on the first call"""
+        self._advance(1)
+        if not self.use_graph:
+            return self._unit()
+        if self.sel_graph is None:
+            c = self.sel
+            self.sel_graph, _ = self._capture(self._unit, [self.static_ids, c.step, c.unfinished, c.count, c.status, c.tokens])
+        self.sel_graph.replay()
+
+    @torch.no_grad()
+    def run_selection(self, n: int, poll_every: int = 8) -> int:
+        """up to n more step_select calls; with eos ids, the device's count of unfinished rows is read after every poll_every-th new
+        token of the generation and the loop ends once it is zero (rows that had finished receive pad meanwhile).  Returns the
+        number of new tokens generated so far (the first one comes from select on the prefill's logits)."""
+        c = self.sel
+        for _ in range(n):
+            if c.eos is not None and c.done % poll_every == 0 and int(c.count) == 0:
+                break
+            self.step_select()
+            c.done += 1
+        return c.done
+
+    def selection_result(self) -> torch.Tensor:
+        """the prompt and the new tokens so far, cut after the column at which the last row finished (what a check after every
+        token would have returned); RuntimeError if a sampled row held NaN or +inf (torch.multinomial raises for such a row)"""
+        c = self.sel
+        status = int(c.status)
+        if status & 1:
+            raise RuntimeError("generate: a row of logits held NaN or +inf (or nothing finite) while sampling")
+        if status & 2:
+            raise RuntimeError("generate: the selection step ran outside the result buffer or the table of uniforms")
+        P, done = c.col0, c.done
+        if c.eos is not None and done:
+            hit = torch.isin(c.tokens[:, P:P + done], c.eos)
+            first = torch.where(hit.any(1), hit.int().argmax(1) + 1, done)
+            done = int(first.max())
+        return c.tokens[:, :P + done]
+
+    def reset(self):
+        """zero the cache rows and positions (the captured step stays valid: same tensors)"""
+        self.cache.reset()
+        self.pos = 0
+
+
+def _generation_limits(model: nn.Module, prompt_len: int, max_length=None, max_new_tokens=None, eos_token_id=None,
+                       pad_token_id=None) -> tuple[int, list, int | None]:
+    """(total length, eos ids, pad id) as model.generate resolves them for greedy decoding: max_new_tokens wins over max_length;
+    without either, the generation config's max_new_tokens, else its max_length NEW tokens (capped at max_position_embeddings);
+    ValueError where nothing is left to generate.  eos defaults to the generation config's, pad to its pad_token_id, else the
+    first eos id"""
+    gc = getattr(model, "generation_config", None)
+    if max_new_tokens is None and max_length is None:
+        max_new_tokens = getattr(gc, "max_new_tokens", None)
+    if max_new_tokens is not None:
+        if int(max_new_tokens) < 1:
+            raise ValueError("generate: max_new_tokens must be >= 1")
+        total = prompt_len + int(max_new_tokens)
+    elif max_length is not None:
+        total = int(max_length)
+    else:                                          # the config's max_length counts NEW tokens then, within max_position_embeddings
+        total = prompt_len + int(getattr(gc, "max_length", None) or 20)
+        cap = getattr(getattr(model, "config", None), "max_position_embeddings", None)
+        total = min(total, cap) if cap is not None else total
+    if total <= prompt_len:
+        raise ValueError(f"Input length of input_ids is {prompt_len}, but `max_length` is set to {total}: set max_new_tokens")
+    if eos_token_id is None:
+        eos_token_id = getattr(gc, "eos_token_id", None)
+    eos = [] if eos_token_id is None else [int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])]
+    if pad_token_id is None:
+        pad_token_id = getattr(gc, "pad_token_id", None)
+    if pad_token_id is None and eos:
+        pad_token_id = eos[0]
+    return total, eos, None if pad_token_id is None else int(pad_token_id)
+
+
+_GREEDY_DEFAULTS = {"do_sample": False, "num_beams": 1, "use_cache": True}
+_SAMPLING_ARGS = ("temperature", "top_k", "top_p")
+
+
+def _sampling_params(model: nn.Module, temperature=None, top_k=None, top_p=None) -> tuple[float, int, float]:
+    """(temperature, top_k, top_p) as model.generate resolves them for do_sample=True: the argument, else the value in
+    model.generation_config, else -- for fields still None -- transformers' GenerationConfig._get_default_generation_params().
+    temperature 1.0, top_k 0 and top_p 1.0 mean "off" (HF builds no warper for them)."""
+    from transformers import GenerationConfig
+    gc = getattr(model, "generation_config", None)
+    defaults = GenerationConfig._get_default_generation_params()
+    vals = []
+    for name, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p)):
+        v = getattr(gc, name, None) if v is None else v
+        vals.append(defaults[name] if v is None else v)
+    return float(vals[0]), int(vals[1]), float(vals[2])
+
+
+@torch.no_grad()
+def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None = None, max_new_tokens: int | None = None,
+             eos_token_id=None, pad_token_id: int | None = None, attention_mask: torch.Tensor | None = None, graph: bool = True,
+             generator: torch.Generator | None = None, uniforms: torch.Tensor | None = None, poll_every: int = 8,
+             **kwargs) -> torch.Tensor:
+    """Decoding of an unpadded batch input_ids [B, P] on the GPU: greedy -- what model.generate(input_ids, do_sample=False, ...)
+    returns -- or, with do_sample=True, sampling with temperature / top_k / top_p (values not passed are resolved as model.generate
+    resolves them: _sampling_params).  The result is the prompt followed by the new tokens, rows that met eos padded with
+    pad_token_id, ending where every row has finished or at the length limit.  One DecodeSession: the prompt is prefilled eagerly,
+    then each token replays ONE captured unit -- the decode step and the HIP token selection (pbl_select_token_f16), which writes
+    the token into the result and into the next step's input and keeps the eos / pad bookkeeping on the device.  The host reads
+    the count of unfinished rows every `poll_every` tokens (never without an eos id); tokens generated after every row finished
+    are pad and are cut off, so the result does not depend on poll_every.
+
+    Sampling draws its uniforms ONCE per call, before the loop: torch.rand([new tokens, B]) from `generator` (default: the default
+    generator of the model's device, so torch.manual_seed(n) reproduces a run), or the caller's table `uniforms` [>= new tokens, B]
+    (values in [0, 1)).  graph=True and graph=False consume the same numbers and give the same tokens.  The token stream for a
+    given seed differs from model.generate's (torch.multinomial consumes the generator differently); the distribution is the same,
+    up to HF's arbitrary choice inside a block of tied values at the top-p boundary.
+
+    Handed to model.generate unchanged: an attention_mask with zeros (a padded batch), a model off the GPU, beams, any other
+    generation argument (repetition_penalty, min_p, ...), do_sample=False together with sampling arguments, and sampling on a model
+    whose logits are not fp16.  model.generate cannot honour `generator` or `uniforms`, so a call that passes one of them and must
+    be handed over raises ValueError.  Greedy decoding of logits that are not fp16 keeps the selection in torch."""
+    sample = kwargs.get("do_sample", False) is True
+    fixed = {k: v for k, v in _GREEDY_DEFAULTS.items() if not (sample and k == "do_sample")}
+    known = set(_GREEDY_DEFAULTS) | (set(_SAMPLING_ARGS) if sample else set())
+    native = all(kwargs[k] == v for k, v in fixed.items() if k in kwargs) and not set(kwargs) - known
+    padded = attention_mask is not None and not bool(attention_mask.all())
+    T, top_k, top_p = 1.0, 0, 1.0                          # greedy: everything off
+    if native and sample:
+        T, top_k, top_p = _sampling_params(model, *(kwargs.get(k) for k in _SAMPLING_ARGS))
+        native = T > 0 and top_k >= 0 and 0 < top_p <= 1 and model.get_input_embeddings().weight.dtype == torch.float16
+
+    def hand_over():
+        if generator is not None or uniforms is not None:
+            raise ValueError("generate: generator= and uniforms= belong to the sampling loop on the GPU (an unpadded batch on a GPU model "
+                             "with fp16 logits, do_sample=True with temperature / top_k / top_p only); model.generate cannot honour them")
+        hf = dict(kwargs)
+        for k, v in (("max_length", max_length), ("max_new_tokens", max_new_tokens), ("eos_token_id", eos_token_id),
+                     ("pad_token_id", pad_token_id), ("attention_mask", attention_mask)):
+            if v is not None:
+                hf[k] = v
+        return model.generate(input_ids, **hf)
+
+    if not native or padded or not input_ids.is_cuda or input_ids.dim() != 2:
+        return hand_over()
+    if poll_every < 1:
+        raise ValueError("generate: poll_every must be >= 1")
+    B, P = input_ids.shape
+    total, eos, pad = _generation_limits(model, P, max_length, max_new_tokens, eos_token_id, pad_token_id)
+    sess = DecodeSession(model, B, total - 1, graph=graph)
+    logits = sess.prefill(input_ids)
+    if logits.dtype == torch.float16 and runtime.select_token_ok(B, logits.shape[1]):
+        table = None
+        if sample:
+            if uniforms is not None:
+                table = uniforms
+            else:                                          # one draw for the whole call; a host generator draws on the host
+                gdev = generator.device if generator is not None else input_ids.device
+                table = torch.rand(total - P, B, generator=generator, device=gdev, dtype=torch.float32)
+        sess.begin_selection(input_ids, total, eos=eos, pad=pad, uniforms=table, temperature=T, top_k=top_k, top_p=top_p)
+        sess.select(logits)
+        sess.sel.done = 1
+        sess.run_selection(total - P - 1, poll_every)
+        return sess.selection_result()
+    if sample:
+        return hand_over()
+    out = [input_ids]
+    eos_t = torch.tensor(eos, dtype=input_ids.dtype, device=input_ids.device) if eos else None
+    unfinished = torch.ones(B, dtype=torch.bool, device=input_ids.device)
+    cur = P
+    while True:
+        nxt = logits.float().argmax(-1).to(input_ids.dtype)
+        if eos_t is not None:
+            nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
+            unfinished &= ~torch.isin(nxt, eos_t)
+        out.append(nxt[:, None])
+        cur += 1
+        if cur >= total or (eos_t is not None and not bool(unfinished.any())):
+            break
+        logits = sess.step(nxt)
+    return torch.cat(out, 1)

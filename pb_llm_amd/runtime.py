@@ -179,6 +179,22 @@ def _rope_layout(qkv: torch.Tensor, q_off: int, k_off: int, batch: int, seq: int
     return got
 
 
+def _rope_form(what: str, qkv: torch.Tensor, heads, batch: int, seq: int, head_dim: int, cos: torch.Tensor, sin: torch.Tensor):
+    """The argument form rope_f16 and rope_append_f16 (`what`) share.  ValueError unless qkv is an fp16 [batch * seq, n] GPU tensor
+    with unit column stride whose rows hold every (column offset, head count) of `heads`.  Returns (ld, the entry's five cos / sin
+    arguments) -- or None where cos / sin are not fp16 [1 or batch, 1 or seq, head_dim] tensors of one layout on qkv's device."""
+    if qkv.dim() != 2 or qkv.dtype != torch.float16 or not qkv.is_cuda or qkv.stride(1) != 1 or qkv.shape[0] != batch * seq:
+        raise ValueError(f"{what}: qkv must be an fp16 [batch * seq, n] GPU tensor with unit column stride")
+    if min(off for off, _ in heads) < 0 or max(off + n * head_dim for off, n in heads) > qkv.shape[1]:
+        raise ValueError(f"{what}: the {' / '.join('qkv'[:len(heads)])} heads must lie inside a row of qkv")
+    if cos.dtype != torch.float16 or sin.dtype != torch.float16 or cos.device != qkv.device or sin.device != qkv.device \
+            or cos.dim() != 3 or cos.shape != sin.shape or cos.stride() != sin.stride() or cos.stride(-1) != 1 \
+            or cos.shape[0] not in (1, batch) or cos.shape[1] not in (1, seq) or cos.shape[-1] != head_dim:
+        return None
+    return qkv.stride(0) if qkv.shape[0] > 1 else qkv.shape[1], (
+        cos.data_ptr(), sin.data_ptr(), head_dim, cos.stride(0) if cos.shape[0] > 1 else 0, cos.stride(1) if cos.shape[1] > 1 else 0)
+
+
 def rope_f16(qkv: torch.Tensor, q_off: int, k_off: int, batch: int, seq: int, n_q: int, n_kv: int, head_dim: int,
              cos: torch.Tensor, sin: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor] | None:
     """HF's apply_rotary_pos_emb(q, k, cos, sin) in ONE launch (pbl_rope_f16) for the q and k heads of a fused q/k/v output: qkv
@@ -186,24 +202,15 @@ def rope_f16(qkv: torch.Tensor, q_off: int, k_off: int, batch: int, seq: int, n_
     (head_dim each); cos / sin [1 or batch, 1 or seq, head_dim] fp16 (position_embeddings).  Returns (q_embed, k_embed) with
     the values, shapes and strides HF's function gives for the views LlamaAttention makes of a fused launch's output -- or None
     where the entry declines (odd head_dim, head_dim > 256) or cos / sin are not of that form: the caller then runs HF's."""
-    if qkv.dim() != 2 or qkv.dtype != torch.float16 or not qkv.is_cuda or qkv.stride(1) != 1 or qkv.shape[0] != batch * seq:
-        raise ValueError("rope_f16: qkv must be an fp16 [batch * seq, n] GPU tensor with unit column stride")
-    if min(q_off, k_off) < 0 or q_off + n_q * head_dim > qkv.shape[1] or k_off + n_kv * head_dim > qkv.shape[1]:
-        raise ValueError("rope_f16: the q / k heads must lie inside a row of qkv")
-    if cos.dtype != torch.float16 or sin.dtype != torch.float16 or cos.device != qkv.device or sin.device != qkv.device \
-            or cos.dim() != 3 or cos.shape != sin.shape or cos.stride() != sin.stride() or cos.stride(-1) != 1 \
-            or cos.shape[0] not in (1, batch) or cos.shape[1] not in (1, seq) or cos.shape[-1] != head_dim \
-            or head_dim % 2 or head_dim > 256:
+    form = _rope_form("rope_f16", qkv, ((q_off, n_q), (k_off, n_kv)), batch, seq, head_dim, cos, sin)
+    if form is None or head_dim % 2 or head_dim > 256:
         return None
     (qs, qst), (ks, kst) = _rope_layout(qkv, q_off, k_off, batch, seq, n_q, n_kv, head_dim, cos, sin)
     if qst[3] != 1 or kst[3] != 1 or qs != (batch, n_q, seq, head_dim) or ks != (batch, n_kv, seq, head_dim):
         return None
     q = torch.empty_strided(qs, qst, dtype=torch.float16, device=qkv.device)
     k = torch.empty_strided(ks, kst, dtype=torch.float16, device=qkv.device)
-    ld = qkv.stride(0) if qkv.shape[0] > 1 else qkv.shape[1]
-    rc = _lib.lib().pbl_rope_f16(qkv.data_ptr(), ld, q_off, k_off, batch, seq, n_q, n_kv, head_dim,
-                                 cos.data_ptr(), sin.data_ptr(), head_dim,
-                                 cos.stride(0) if cos.shape[0] > 1 else 0, cos.stride(1) if cos.shape[1] > 1 else 0,
+    rc = _lib.lib().pbl_rope_f16(qkv.data_ptr(), form[0], q_off, k_off, batch, seq, n_q, n_kv, head_dim, *form[1],
                                  q.data_ptr(), (C.c_int64 * 3)(*qst[:3]), k.data_ptr(), (C.c_int64 * 3)(*kst[:3]),
                                  torch.cuda.current_stream(qkv.device).cuda_stream)
     if rc == _lib.PBL_ERR_UNSUPPORTED:
@@ -236,26 +243,17 @@ def rope_append_f16(qkv: torch.Tensor, q_off: int, k_off: int, v_off: int, batch
     heads (n_kv heads from column v_off of qkv) written into rows [pos, pos + seq) of the layer's static cache k_cache / v_cache
     [batch, n_kv, max_len, head_dim] fp16; pos (int64, on the device, read there) is not changed.  None where the entry declines
     (head_dim not 64 / 128, seq > 4, batch > 4, n_q % n_kv) or cos / sin are not of rope_f16's form."""
-    if qkv.dim() != 2 or qkv.dtype != torch.float16 or not qkv.is_cuda or qkv.stride(1) != 1 or qkv.shape[0] != batch * seq:
-        raise ValueError("rope_append_f16: qkv must be an fp16 [batch * seq, n] GPU tensor with unit column stride")
-    if min(q_off, k_off, v_off) < 0 or max(q_off + n_q * head_dim, k_off + n_kv * head_dim, v_off + n_kv * head_dim) > qkv.shape[1]:
-        raise ValueError("rope_append_f16: the q / k / v heads must lie inside a row of qkv")
+    form = _rope_form("rope_append_f16", qkv, ((q_off, n_q), (k_off, n_kv), (v_off, n_kv)), batch, seq, head_dim, cos, sin)
     B, Hkv, max_len, D = _cache_args(k_cache, v_cache, pos, qkv.device, "rope_append_f16")
     if (B, Hkv, D) != (batch, n_kv, head_dim):
         raise ValueError("rope_append_f16: the cache is not [batch, n_kv, max_len, head_dim]")
-    if cos.dtype != torch.float16 or sin.dtype != torch.float16 or cos.device != qkv.device or sin.device != qkv.device \
-            or cos.dim() != 3 or cos.shape != sin.shape or cos.stride() != sin.stride() or cos.stride(-1) != 1 \
-            or cos.shape[0] not in (1, batch) or cos.shape[1] not in (1, seq) or cos.shape[-1] != head_dim \
-            or not decode_attention_ok(batch, seq, n_q, n_kv, head_dim, max_len):
+    if form is None or not decode_attention_ok(batch, seq, n_q, n_kv, head_dim, max_len):
         return None
     (qs, qst), _ = _rope_layout(qkv, q_off, k_off, batch, seq, n_q, n_kv, head_dim, cos, sin)
     if qst[3] != 1 or qs != (batch, n_q, seq, head_dim):
         return None
     q = torch.empty_strided(qs, qst, dtype=torch.float16, device=qkv.device)
-    ld = qkv.stride(0) if qkv.shape[0] > 1 else qkv.shape[1]
-    rc = _lib.lib().pbl_rope_append_f16(qkv.data_ptr(), ld, q_off, k_off, v_off, batch, seq, n_q, n_kv, head_dim,
-                                        cos.data_ptr(), sin.data_ptr(), head_dim,
-                                        cos.stride(0) if cos.shape[0] > 1 else 0, cos.stride(1) if cos.shape[1] > 1 else 0,
+    rc = _lib.lib().pbl_rope_append_f16(qkv.data_ptr(), form[0], q_off, k_off, v_off, batch, seq, n_q, n_kv, head_dim, *form[1],
                                         q.data_ptr(), (C.c_int64 * 3)(*qst[:3]), k_cache.data_ptr(), v_cache.data_ptr(), max_len,
                                         pos.data_ptr(), torch.cuda.current_stream(qkv.device).cuda_stream)
     if rc == _lib.PBL_ERR_UNSUPPORTED:

@@ -367,10 +367,10 @@ def test_the_loop_stays_on_the_device(epi, with_eos, poll):
     sess = H.DecodeSession(epi, 1, 5 + n, graph=True)
     sess.begin_selection(ids, 5 + n, eos=[1001] if with_eos else (), pad=0, uniforms=U, temperature=0.7, top_k=50, top_p=0.9)
     sess.select(sess.prefill(ids))
-    sess.sel["done"] = 1
+    sess.sel.done = 1
     assert sess.run_selection(3, poll) == 4                                  # the capture happens here
     ops = count_ops(lambda: sess.run_selection(32, poll))
-    assert sess.sel["done"] == 36
+    assert sess.sel.done == 36
     for op in ("aten::argmax", "aten::sort", "aten::multinomial", "aten::isin", "aten::cumsum", "aten::topk", "aten::softmax"):
         assert op not in ops, op
     reads = ops.get("aten::_local_scalar_dense", 0)

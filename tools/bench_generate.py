@@ -2,7 +2,7 @@
 """Greedy decode over a KV cache at context 128 / 1024 / 4096 on a llama-7b-shaped HF model (4096 / 11008 / 32 heads, distinct
 packed weights per layer as in bench_decode_prologues.py, fuse_decode_(epilogues=True)), three cases alternated in one process:
   hf       HF's DynamicCache, eager (what model.generate runs per token)
-  static   harness.DecodeSession with harness.DECODE_ATTENTION = False: HF's StaticLayer.update and SDPA over all max_len rows
+  static   harness.DecodeSession with decoding.DECODE_ATTENTION = False: HF's StaticLayer.update and SDPA over all max_len rows
            behind the mask, the step replayed from a hipGraph
   kernels  harness.DecodeSession: rope_append_f16 + decode_attention_f16 in the folded layers, the same graph replay
 Per case and context: us per token (median over reps of `iters` tokens from the same context: the session's positions / the
@@ -22,7 +22,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from transformers import DynamicCache, LlamaConfig, LlamaForCausalLM  # noqa: E402
 
-from pb_llm_amd import harness as H, ptq  # noqa: E402
+from pb_llm_amd import decoding, harness as H, ptq  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--layers", type=int, default=6)
@@ -90,7 +90,7 @@ class HFCase:
 
 class SessionCase:
     def __init__(self, C, kernels, graph=True):
-        H.DECODE_ATTENTION = kernels
+        decoding.DECODE_ATTENTION = kernels
         try:
             self.C, self.sess = C, H.DecodeSession(model, 1, C + args.iters + 4, graph=graph)
             self.sess.prefill(ids[:, :C])
@@ -99,7 +99,7 @@ class SessionCase:
             self.first = self.step(C).float().clone()
             self.rewind()
         finally:
-            H.DECODE_ATTENTION = True
+            decoding.DECODE_ATTENTION = True
 
     def rewind(self):
         for lay in self.sess.cache.layers:
@@ -126,11 +126,11 @@ with torch.no_grad():
             elif f"{k}_kernels_per_token" not in out:
                 e = SessionCase(min(contexts), k == "kernels", graph=False)
                 e.rewind()
-                H.DECODE_ATTENTION = k == "kernels"            # (an eager step reads the switch when it runs)
+                decoding.DECODE_ATTENTION = k == "kernels"            # (an eager step reads the switch when it runs)
                 try:
                     out[f"{k}_kernels_per_token"] = count_kernels(lambda: e.step(min(contexts)))
                 finally:
-                    H.DECODE_ATTENTION = True
+                    decoding.DECODE_ATTENTION = True
                 del e
         times = {k: [] for k in runs}
         for k, r in runs.items():                          # warm-up
