@@ -66,6 +66,53 @@ def test_restatement_matches_direct_softmax(B, S, Hq, Hkv, D, pos):
     np.testing.assert_allclose(decode_attn_ref(q, k, v, pos, D ** -0.5), direct_attn(q, k, v, pos, D ** -0.5), rtol=1e-12, atol=1e-12)
 
 
+@pytest.mark.parametrize("chunk", [64, 96, 512])
+@pytest.mark.parametrize("B,S,Hq,Hkv,D", [(1, 1, 2, 2, 8), (2, 4, 4, 2, 16)])
+def test_restatement_matches_direct_softmax_at_the_larger_chunks(B, S, Hq, Hkv, D, chunk):
+    """the chunk sizes the GPU tests rely on beyond 32, at positions past one chunk: a split boundary inside the S rows, one key
+    into the second split, and several splits with a cut-short last one"""
+    rng = np.random.default_rng(chunk + 10 * B + S)
+    for pos in (chunk - 2, chunk, 2 * chunk + chunk // 2 + 3):
+        L = pos + S + 7
+        q = rng.standard_normal((B, Hq, S, D)) * 2
+        k, v = rng.standard_normal((B, Hkv, L, D)), rng.standard_normal((B, Hkv, L, D))
+        np.testing.assert_allclose(decode_attn_ref(q, k, v, pos, D ** -0.5, chunk), direct_attn(q, k, v, pos, D ** -0.5),
+                                   rtol=1e-12, atol=1e-12)
+
+
+# ---------------------------------------------------------------- the split plan
+def split_plan(max_len):
+    """(chunk, nsplit) of pbl_decode_attn_f16: keys per split and splits"""
+    chunk = 32 * -(-max_len // 4096)
+    return chunk, -(-max_len // chunk)
+
+
+def test_split_plan_over_every_supported_length():
+    L = _lib.lib()
+    shapes = [(1, 1, 8, 128), (4, 4, 32, 64), (2, 3, 4, 128)]
+    for max_len in range(1, 65537):
+        chunk, nsplit = split_plan(max_len)
+        assert chunk <= 512 and nsplit <= 128 and chunk * nsplit >= max_len, max_len
+        for B, S, Hq, D in shapes:
+            assert L.pbl_decode_attn_workspace_bytes(B, S, Hq, D, max_len) == B * Hq * S * nsplit * (2 + D) * 4, (max_len, B, S, Hq, D)
+    assert split_plan(4096) == (32, 128) and split_plan(4097) == (64, 65) and split_plan(65536) == (512, 128)
+
+
+def test_decode_attention_declines_65537_rows_before_any_launch():
+    from pb_llm_amd import runtime as R
+    L = _lib.lib()
+    rows, D = 65537, 64
+    keep = [(C.c_uint16 * (rows * D + 8))() for _ in range(2)] + [(C.c_uint16 * (1 << 15))() for _ in range(3)]   # k, v; q, out, ws
+    kc, vc, q, out, ws = (C.addressof(b) + (-C.addressof(b)) % 16 for b in keep)
+    pos = (C.c_int64 * 1)(0)
+    need = L.pbl_decode_attn_workspace_bytes(1, 1, 1, D, rows)
+    assert 0 < need <= (1 << 16) - 16
+    assert L.pbl_decode_attn_f16(q, (C.c_int64 * 3)(D, D, D), kc, vc, 1, 1, 1, 1, D, rows, 0.125, C.addressof(pos), out, D, ws, need,
+                                 None) == _lib.PBL_ERR_UNSUPPORTED
+    assert pos[0] == 0
+    assert R.decode_attention_ok(1, 1, 1, 1, D, 65536) and not R.decode_attention_ok(1, 1, 1, 1, D, rows)
+
+
 # ---------------------------------------------------------------- the C ABI
 def test_new_entries_are_declared_and_exported():
     hdr = open(os.path.join(REPO, "include", "pbl.h")).read()

@@ -99,13 +99,24 @@ def test_decode_attention_declines():
 @pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("B,S", [(1, 1), (1, 2), (1, 3), (1, 4), (2, 1), (2, 2), (4, 1)])
 def test_rope_append_equals_hf(B, S, D):
+    check_rope_append(B, S, D, 8, 2, 512, (0, 5, 512 - S))
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("B,S", [(1, 1), (4, 4)])
+def test_rope_append_equals_hf_at_65536_rows(B, S, D):
+    """the largest cache the entries accept, the last rows of its last head: the cache index ((b Hkv + hh) max_len + row) D reaches
+    4 * 8 * 65536 * 128 = 2^28 elements"""
+    check_rope_append(B, S, D, 8, 8, 65536, (65536 - S - 1, 65536 - S))
+
+
+def check_rope_append(B, S, D, Hq, Hkv, L, positions):
     from transformers import LlamaConfig
     from transformers.models.llama.modeling_llama import apply_rotary_pos_emb
-    Hq, Hkv, L = 8, 2, 512
     cfg = LlamaConfig(hidden_size=Hq * D, num_attention_heads=Hq, num_key_value_heads=Hkv, max_position_embeddings=131072)
     y, q, k = qkv_out(B, S, Hq, Hkv, D, 31 * B + S + D)
     v = y[:, (Hq + Hkv) * D:].reshape(B, S, Hkv, D).transpose(1, 2)
-    for pos in (0, 5, L - S):
+    for pos in positions:
         cos, sin = cos_sin(cfg, [[pos + s for s in range(S)]], DEV)
         kc0 = torch.randn(B, Hkv, L, D, device=DEV).half()
         vc0 = torch.randn(B, Hkv, L, D, device=DEV).half()
@@ -275,6 +286,42 @@ def test_folded_step_runs_the_new_kernels_only(epi):
     names = " ".join(e.name for e in prof.events())
     for kern in ("pbl_rope_append_kernel", "pbl_attn_partial_kernel", "pbl_attn_combine_kernel"):
         assert kern in names, kern
+
+
+def step_kernels(model, seq, P):
+    """the GPU kernels' names in one eager session step at position P, after a prefill of seq[:, :P]"""
+    from torch.profiler import ProfilerActivity, profile
+    sess = H.DecodeSession(model, seq.shape[0], seq.shape[1], graph=False)
+    sess.prefill(seq[:, :P])
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        sess.step(seq[:, P])
+        torch.cuda.synchronize()
+    return " ".join(e.name for e in prof.events())
+
+
+def test_session_across_position_4096_equals_hf_attention():
+    """a session of 4120 positions (chunk 64, 65 splits: what tools/bench_generate.py measures at context 4096): 4090 tokens
+    prefilled, then teacher-forced steps across position 4096 -- the HIP decode attention against the same model and session
+    over HF's StaticLayer and SDPA, at the bound this file applies to session-vs-HF logits"""
+    from pb_llm_amd import decoding
+    model = gqa_llama(max_positions=4224)
+    assert H.fuse_decode_(model, epilogues=True) == 4
+    P, n = 4090, 4120
+    seq = ids_of(n, 23)
+    assert "pbl_attn_partial_kernel" in step_kernels(model, seq, P)
+    on = session_logits(model, seq, P)
+    was = decoding.DECODE_ATTENTION
+    decoding.DECODE_ATTENTION = False
+    try:
+        off = session_logits(model, seq, P)
+        assert "pbl_attn_partial_kernel" not in step_kernels(model, seq, P)
+    finally:
+        decoding.DECODE_ATTENTION = was
+    assert on.shape == off.shape == (1, n - P, 1000) and bool(torch.isfinite(on).all())
+    diff = float((on - off).abs().max())
+    rel = diff / float(off.abs().max())
+    print(f"[long context] P={P}, {n - P - 1} steps across position 4096: logits rel {rel:.2e} (abs {diff:.2e}) against HF's attention")
+    assert rel < 1e-2
 
 
 def test_generate_without_the_kernels_reproduces_hf():

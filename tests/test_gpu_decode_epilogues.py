@@ -194,15 +194,19 @@ def test_residual_epilogue_declines(o_proj):
 
 
 # ---------------------------------------------------------------- model level
-def gqa_llama(seed=3):
+def gqa_config(max_positions=256):
+    from transformers import LlamaConfig
+    return LlamaConfig(hidden_size=512, intermediate_size=1408, num_hidden_layers=2, num_attention_heads=8,
+                       num_key_value_heads=2, vocab_size=1000, max_position_embeddings=max_positions)
+
+
+def gqa_llama(seed=3, max_positions=256):
     """the 2-layer model of test_gpu_decode_prologues.llama with 8 q heads and 2 kv heads"""
-    from transformers import LlamaConfig, LlamaForCausalLM
+    from transformers import LlamaForCausalLM
     from oracle import pb_oracle as O
     from pb_llm_amd import harness as H
     torch.manual_seed(seed)
-    cfg = LlamaConfig(hidden_size=512, intermediate_size=1408, num_hidden_layers=2, num_attention_heads=8,
-                      num_key_value_heads=2, vocab_size=1000, max_position_embeddings=256)
-    model = LlamaForCausalLM(cfg).half().eval()
+    model = LlamaForCausalLM(gqa_config(max_positions)).half().eval()
     with torch.no_grad():
         for n, p in model.named_parameters():
             if "norm" in n:
