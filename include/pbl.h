@@ -565,6 +565,34 @@ int pbl_select_token_f16(const void* logits, int64_t ld, int B, int V, float tem
                          int64_t* tokens, int64_t total, int64_t col0, int64_t* next_ids, int32_t* n_unfinished, int32_t* status,
                          uint8_t* kept, void* stream);
 
+/* Token scoring of an evaluation pass (csrc/pbl_score.hip; scoring.token_logprobs / scoring.loglikelihood / harness.perplexity(fused=
+ * True)): per row of logits the log-probability of a target token and whether it is the arg-max, and per request the sum / AND over
+ * a span of rows -- one read of the fp16 logits, one workgroup per row, then (R > 0) one wave per span in a second launch.
+ *   logits [T, V] fp16, row t at logits + t ld elements (ld >= V, unit column stride, any alignment: chunks of 16 bytes are laid from
+ *   the 16-byte boundary below each row's start, the row's two edge chunks take element loads); targets [T] int64; logprob [T] fp32;
+ *   greedy [T] bytes (may be NULL when R = 0).  Per row:
+ *     1. a row that holds a NaN or a +inf, or no finite value, scores NaN for every target (torch.log_softmax(row.float(), -1));
+ *     2. else logprob[t] = float(x[target]) - lse, lse = m + log(sum exp(x_i - m)) in fp32, m the row's maximum (online softmax over
+ *        256 lanes, merged in a fixed order: bit-stable from run to run, eager or replayed; a partial whose maximum is -inf is
+ *        never rescaled, so exp(-inf - -inf) is not evaluated);
+ *     3. a finite row whose target element is -inf scores -inf;
+ *     4. greedy[t] = 1 iff target is the lowest index among the row's maxima; -0 equals +0 and a NaN counts as the maximum (rule 5
+ *        of pbl_select_token_f16, torch.argmax) -- an integer comparison on fp16 keys, exact, also for rows that score NaN;
+ *     5. targets[t] == ignore_index: logprob = 0, greedy = 0, the row is not read and not counted in spans;
+ *     6. any other target outside [0, V): logprob = NaN, greedy = 0, bit 0 of *status; the row is not indexed.
+ *   spans [R, 2] int64 row ranges [begin, end) (may overlap; NULL with R = 0): span_sum[r] (fp64) = the sum of logprob over the
+ *   counted rows -- lane j of one wave adds rows begin + j, begin + j + 64, ... in order, then the 64 partials are added by a xor
+ *   butterfly (32, 16, ... 1) --, span_greedy[r] (byte) = the AND of greedy over them, span_count[r] (int32) = their number.  An empty
+ *   or fully ignored span: 0, 1, 0.  A span with begin < 0, end > T or begin > end reads nothing: NaN, 0, 0 and bit 1 of *status.
+ *   *status (int32) is only ever OR-ed into.
+ * PBL_ERR_INVALID_ARG for NULL pointers (greedy may be NULL when R = 0; spans and the three span outputs may be NULL when R = 0),
+ * T < 1, V < 1, R < 0, ld < V and outputs overlapping inputs or each other, before any device work; PBL_ERR_UNSUPPORTED for
+ * V > 1048576 or T > INT_MAX.  No workspace, no allocation, no synchronisation, nothing read on the host, no floating-point atomics:
+ * capturable in a hipGraph. */
+int pbl_score_tokens_f16(const void* logits, int64_t ld, int64_t T, int V, const int64_t* targets, int64_t ignore_index,
+                         float* logprob, uint8_t* greedy, const int64_t* spans, int R, double* span_sum, uint8_t* span_greedy,
+                         int32_t* span_count, int32_t* status, void* stream);
+
 /* ---------------- QAT step, weight side ------------------------------------------ */
 /* The elementwise work of one training step of BinaryXnorExceptOutliersLinear
  * (quant/outlier_quantizer.py:83-99; straight-through estimator quant/quantizer.py:18-25), fused into

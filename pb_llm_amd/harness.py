@@ -7,17 +7,19 @@ fake-quant weight, swap in PBLinear modules, run forward / perplexity-style loop
 stays resident in HBM (288 GB: no layer-by-layer host offload), every decoder Linear is quantised by the fused
 GPTQ-PB pipeline (pb_llm_amd/ptq.py) and, optionally, packed on the spot.
 `quantize_dense_` takes an external structure producer instead (tests pass the oracle's).
-Decode fusion (`fuse_decode_`) lives in fusion.py and generation (`DecodeSession`, `generate`) in decoding.py; re-exported here.
+Decode fusion (`fuse_decode_`) lives in fusion.py, generation (`DecodeSession`, `generate`) in decoding.py and continuation scoring
+(`token_logprobs`, `loglikelihood`) in scoring.py; re-exported here.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from . import decoding, quant as Q
+from . import decoding, quant as Q, scoring
 from .decoding import DecodeSession, _generation_limits, _sampling_params, generate  # noqa: F401
 from .fusion import FUSE_SETS, _DeferredNorm, _FoldedMLP, _FusedGroup, _FusedMember, fuse_decode_  # noqa: F401
 from .quant import PBLinear, replace_linear_with_pb
+from .scoring import _batches, loglikelihood, token_logprobs  # noqa: F401
 
 
 def __getattr__(name):                   # harness.DecodeCache: the class decoding.py builds on first use (transformers stays lazy)
@@ -232,9 +234,13 @@ class GraphedForward:
 
 
 @torch.no_grad()
-def perplexity(model: nn.Module, input_ids: torch.Tensor, seqlen: int) -> float:
+def perplexity(model: nn.Module, input_ids: torch.Tensor, seqlen: int, fused: bool = False) -> float:
     """The loop of gptq_pb/eval_ppl_utils.py:55-86 / evaluate.py:126-156 on pre-tokenised ids
-    [1, n*seqlen]: mean NLL over non-overlapping windows -> exp."""
+    [1, n*seqlen]: mean NLL over non-overlapping windows -> exp.  fused=True: every window's fp16 logits are scored by one HIP
+    call over the view logits[0, :-1] (no fp32 copy, no cross_entropy) and the host reads once, after the last window
+    (scoring.perplexity_fused)."""
+    if fused:
+        return scoring.perplexity_fused(model, input_ids, seqlen)
     n = input_ids.numel() // seqlen
     nll = 0.0
     for i in range(n):

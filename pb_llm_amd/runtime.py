@@ -343,3 +343,52 @@ def select_token_f16(logits: torch.Tensor, step: torch.Tensor, unfinished: torch
         return None
     _lib.check(rc, "token selection")
     return True
+
+
+SCORE_MAX_VOCAB = 1 << 20
+
+
+def score_tokens_ok(T: int, V: int) -> bool:
+    """the scope of score_tokens_f16 (pbl_score_tokens_f16): any number of rows below 2^31, a vocabulary of at most 2^20 words"""
+    return 1 <= T < (1 << 31) and 1 <= V <= SCORE_MAX_VOCAB
+
+
+def score_tokens_f16(logits: torch.Tensor, targets: torch.Tensor, spans: torch.Tensor | None = None, ignore_index: int = -100):
+    """log p(targets[t] | row t) and "targets[t] is the arg-max of row t" for every row of logits [T, V] fp16, in ONE read of the
+    logits (pbl_score_tokens_f16; the rules are in include/pbl.h).  logits: any 2-D fp16 GPU view with unit column stride and a row
+    stride >= V -- out.logits[0, :-1] and out.logits[0, :-1, :50257] as they are; it is never copied or converted.  targets: int64
+    [T] on the logits' device; rows whose target is ignore_index score 0 / False and are not read.  spans: int64 [R, 2] row ranges
+    [begin, end) on the device, or None.  Returns (logprob fp32 [T], greedy bool [T], span_sum fp64 [R] | None, span_greedy bool [R]
+    | None, span_count int32 [R] | None, status int32 [1]); status bit 0: a target outside [0, V) (its row scores NaN), bit 1: a
+    span outside [0, T] (its sum is NaN).  Nothing is read on the host: capturable in a hipGraph.  None where the entry declines
+    (score_tokens_ok)."""
+    if not logits.is_cuda or logits.dim() != 2 or logits.dtype != torch.float16 or logits.stride(1) != 1 or logits.shape[1] < 1 \
+            or logits.shape[0] < 1 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        raise ValueError("score_tokens_f16: logits must be an fp16 [T, V] GPU tensor with unit column stride and a row stride >= V")
+    T, V = (int(d) for d in logits.shape)
+    dev = logits.device
+    if targets.device != dev or targets.dtype != torch.int64 or targets.dim() != 1 or targets.numel() != T or not targets.is_contiguous():
+        raise ValueError("score_tokens_f16: targets must be a contiguous int64 [T] tensor on the logits' device")
+    if spans is not None and (spans.device != dev or spans.dtype != torch.int64 or spans.dim() != 2 or spans.shape[1] != 2
+                              or not spans.is_contiguous()):
+        raise ValueError("score_tokens_f16: spans must be a contiguous int64 [R, 2] tensor on the logits' device")
+    if not score_tokens_ok(T, V):
+        return None
+    R = 0 if spans is None else int(spans.shape[0])
+    logprob = torch.empty(T, dtype=torch.float32, device=dev)
+    greedy = torch.empty(T, dtype=torch.bool, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    span_sum = span_greedy = span_count = None
+    if spans is not None:
+        span_sum = torch.empty(R, dtype=torch.float64, device=dev)
+        span_greedy = torch.empty(R, dtype=torch.bool, device=dev)
+        span_count = torch.empty(R, dtype=torch.int32, device=dev)
+    rc = _lib.lib().pbl_score_tokens_f16(
+        logits.data_ptr(), logits.stride(0) if T > 1 else V, T, V, targets.data_ptr(), int(ignore_index), logprob.data_ptr(),
+        greedy.data_ptr(), spans.data_ptr() if R else None, R, span_sum.data_ptr() if R else None,
+        span_greedy.data_ptr() if R else None, span_count.data_ptr() if R else None, status.data_ptr(),
+        torch.cuda.current_stream(dev).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "token scoring")
+    return logprob, greedy, span_sum, span_greedy, span_count, status
