@@ -239,6 +239,14 @@ int pbl_unpack_dense_f32(const void* host_blob, size_t bytes, float* W_out);
  * (informational; the launchers compute it themselves). */
 size_t pbl_gemv_lds_bytes(const pbl_layer* layer, int m);
 
+/* Host only, no device work: the configuration of pbl_gemv_kernel a group-free GEMV launch gets -- *split waves share a record
+ * (8, 4, 2: latency mode; 1: a wave per record) in workgroups of *wpb waves.  NRB records of 16 rows, P = ceil(K / 512) panels.
+ * members == 0: the single-layer entries (pbl_linear_f16 up to one pass, pbl_linear_bf16, pbl_linear_f16_swiglu,
+ * pbl_linear_f16_residual, pbl_linear_f16_swiglu_residual).  members == L >= 1: a fused or grouped launch of L members whose
+ * largest has NRB records (pbl_gemv_f16_fused*, pbl_gemv_bf16_fused_host, pbl_gemv_f16_grouped).  The launchers ask the same
+ * helper, so the answer is what runs.  PBL_ERR_INVALID_ARG: NULL outputs, members < 0, NRB or P of 0. */
+int pbl_gemv_route(uint32_t NRB, uint32_t P, int members, int* split, int* wpb);
+
 /* y[M,N] = x[M,K] @ W_sim^T + bias.  x, y: device fp16, row-major, contiguous
  * (replaces F.linear(x, w_sim, bias): quant/outlier_quantizer.py:105,
  * quant/quantizer.py:86,193).  M >= 1: up to PBL_MAX_TOKENS_PER_LAUNCH tokens run on the bit-unpacking GEMV,

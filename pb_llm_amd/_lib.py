@@ -62,7 +62,7 @@ EXPORTS = ["pbl_status_string", "pbl_version", "pbl_pack_dense_f32", "pbl_pack_d
            "pbl_gemm_f16_image_ws", "pbl_gemv_f16_fused_norm_host", "pbl_linear_f16_swiglu",
            "pbl_linear_f16_residual", "pbl_linear_f16_swiglu_residual", "pbl_rope_f16",
            "pbl_rope_append_f16", "pbl_decode_attn_workspace_bytes", "pbl_decode_attn_f16", "pbl_select_token_f16",
-           "pbl_score_tokens_f16"]
+           "pbl_score_tokens_f16", "pbl_gemv_route"]
 
 
 def lib() -> C.CDLL:
@@ -94,6 +94,8 @@ def lib() -> C.CDLL:
     L.pbl_unpack_dev.argtypes = [C.POINTER(PblLayer), vp, C.c_int, vp]
     L.pbl_gemv_lds_bytes.restype = sz
     L.pbl_gemv_lds_bytes.argtypes = [C.POINTER(PblLayer), C.c_int]
+    L.pbl_gemv_route.restype = C.c_int
+    L.pbl_gemv_route.argtypes = [u32, u32, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.pbl_linear_f16.restype = C.c_int
     L.pbl_linear_f16.argtypes = [C.POINTER(PblLayer), vp, vp, C.c_int, C.c_int, vp]
     L.pbl_gemm_mfma_f16.restype = C.c_int

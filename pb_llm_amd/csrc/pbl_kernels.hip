@@ -1298,6 +1298,24 @@ int pick_split(uint32_t records, uint32_t P) {
     return s;
 }
 
+#ifndef PBL_GROUPED_WPB
+#define PBL_GROUPED_WPB 4
+#endif
+// THE launch configuration of a group-free GEMV pass (pbl_gemv_route answers from here, so it cannot drift from what is launched).
+// members == 0: one layer of NRB records (route_of: throughput mode, a wave per record and 4 per workgroup, when the records fill
+// the chip; otherwise latency mode, S waves share a record).  members == L >= 1: a fused / grouped launch of L members whose
+// largest has NRB records (few records in total -- fused q/k/v, gate+up at decode time -- run latency mode).
+struct GemvRoute {
+    int split, wpb;   // waves per record, waves per workgroup
+};
+GemvRoute gemv_route(uint32_t NRB, uint32_t P, int members) {
+    GemvRoute g;
+    const uint64_t records = uint64_t(NRB) * uint64_t(members > 0 ? members : 1);
+    g.split = records >= PBL_SPLIT_TARGET_WAVES ? 1 : pick_split(uint32_t(records), P);
+    g.wpb = g.split > 1 ? g.split : members > 0 ? PBL_GROUPED_WPB : (NRB >= 1024 ? 4 : 1);
+    return g;
+}
+
 // [a, a + na) and [b, b + nb) share a byte
 bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
@@ -1426,6 +1444,14 @@ size_t pbl_gemv_lds_bytes(const pbl_layer* layer, int m) {
     return lds_bytes(layer->P, layer->max_nch, m, 4);
 }
 
+// Host only: which pbl_gemv_kernel configuration a group-free launch gets (gemv_route, the helper every launcher asks).
+int pbl_gemv_route(uint32_t NRB, uint32_t P, int members, int* split, int* wpb) {
+    if (!split || !wpb || members < 0 || !NRB || !P) return PBL_ERR_INVALID_ARG;
+    const GemvRoute g = gemv_route(NRB, P, members);
+    *split = g.split; *wpb = g.wpb;
+    return PBL_OK;
+}
+
 int pbl_linear_f16(const pbl_layer* layer, const void* x, void* y, int M, int y_f32, void* stream) {
     return pbl_linear_f16_ws(layer, x, y, M, y_f32, nullptr, 0, stream);
 }
@@ -1450,8 +1476,8 @@ static Route route_of(const pbl_layer* layer, int M, bool x_aligned) {
     } else {
         // throughput mode (a wave per record, 4 per workgroup) when there are enough records to fill the
         // chip; otherwise latency mode: S waves share a record
-        r.split = layer->NRB >= PBL_SPLIT_TARGET_WAVES ? 1 : pick_split(layer->NRB, layer->P);
-        r.wpb = r.split > 1 ? r.split : (layer->NRB >= 1024 ? 4 : 1);
+        const GemvRoute g = gemv_route(layer->NRB, layer->P, 0);
+        r.split = g.split; r.wpb = g.wpb;
         r.mb_max = PBL_MAX_TOKENS_PER_LAUNCH;
         while (r.mb_max > 1 && lds_bytes(layer->P, layer->max_nch, r.mb_max, r.wpb, r.split) > PBL_GEMV_LDS_BUDGET) --r.mb_max;
     }
@@ -1786,14 +1812,12 @@ int pbl_gemv_f16_grouped(const pbl_layer* layers_dev, const void* const* x_dev, 
     GemvArgs a{};
     a.layers = layers_dev; a.xs = x_dev; a.ys = y_dev; a.M = M; a.y_f32 = y_f32; a.grouped = 1; a.Lc = Lc;
     if (any_groups & 1) return grouped_groups(a, M, max_NRB, max_K, max_nch, static_cast<hipStream_t>(stream));
-#ifndef PBL_GROUPED_WPB
-#define PBL_GROUPED_WPB 4
-#endif
     const uint32_t P = (max_K + PBL_PANEL_COLS - 1) / PBL_PANEL_COLS;
     const bool sf = (any_groups & 2) != 0;   // bit 1: the group may contain PBL_FLAG_SAL_F16 layers
     hipStream_t st = static_cast<hipStream_t>(stream);
     // few records in total (fused q/k/v, gate+up at decode time): latency mode, S waves per record
-    const int split = uint64_t(max_NRB) * uint64_t(Lc) >= PBL_SPLIT_TARGET_WAVES ? 1 : pick_split(max_NRB * uint32_t(Lc), P);
+    const GemvRoute g = gemv_route(max_NRB, P, Lc);
+    const int split = g.split;
     if (split > 1) {
         const dim3 grid(max_NRB, Lc, 1);
         const size_t lds = lds_bytes(P, max_nch, M, split, split);
@@ -1803,7 +1827,7 @@ int pbl_gemv_f16_grouped(const pbl_layer* layers_dev, const void* const* x_dev, 
             default: return launch_split<2>(M, sf, a, grid, lds, st);
         }
     }
-    const int wpb = PBL_GROUPED_WPB;
+    const int wpb = g.wpb;                    // (PBL_GROUPED_WPB: the instantiation below)
     const dim3 grid((max_NRB + wpb - 1) / wpb, Lc, 1);
     return launch_mb<PBL_GROUPED_WPB>(M, sf, a, grid, lds_bytes(P, max_nch, M, wpb), st);
 }
@@ -1877,8 +1901,8 @@ static int fused_launch_norm(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint3
     const uint32_t P = (K + PBL_PANEL_COLS - 1) / PBL_PANEL_COLS;
     const bool sf = (group_flags & 2) != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int split = uint64_t(max_NRB) * uint64_t(Lc) >= PBL_SPLIT_TARGET_WAVES ? 1 : pick_split(max_NRB * uint32_t(Lc), P);
-    const int wpb = split > 1 ? split : PBL_GROUPED_WPB;
+    const GemvRoute g = gemv_route(max_NRB, P, Lc);
+    const int split = g.split, wpb = g.wpb;   // (split == 1: PBL_GROUPED_WPB, the instantiation below)
     const size_t lds = split > 1 ? lds_bytes(P, max_nch, M, split, split) : lds_bytes(P, max_nch, M, wpb);
     if (lds > PBL_GEMV_LDS_BUDGET) return PBL_ERR_UNSUPPORTED;
     const dim3 grid(split > 1 ? max_NRB : (max_NRB + wpb - 1) / wpb, Lc, 1);
@@ -1897,7 +1921,8 @@ static int fused_launch(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K
     const uint32_t P = (K + PBL_PANEL_COLS - 1) / PBL_PANEL_COLS;
     const bool sf = (group_flags & 2) != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int split = uint64_t(max_NRB) * uint64_t(Lc) >= PBL_SPLIT_TARGET_WAVES ? 1 : pick_split(max_NRB * uint32_t(Lc), P);
+    const GemvRoute g = gemv_route(max_NRB, P, Lc);
+    const int split = g.split;
     if (split > 1) {
         const dim3 grid(max_NRB, Lc, 1);
         const size_t lds = lds_bytes(P, max_nch, M, split, split);
@@ -1907,7 +1932,7 @@ static int fused_launch(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K
             default: return launch_split<2>(M, sf, a, grid, lds, st);
         }
     }
-    const int wpb = PBL_GROUPED_WPB;
+    const int wpb = g.wpb;                    // (PBL_GROUPED_WPB: the instantiation below)
     const dim3 grid((max_NRB + wpb - 1) / wpb, Lc, 1);
     return launch_mb<PBL_GROUPED_WPB>(M, sf, a, grid, lds_bytes(P, max_nch, M, wpb), st);
 }
