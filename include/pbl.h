@@ -601,6 +601,46 @@ int pbl_score_tokens_f16(const void* logits, int64_t ld, int64_t T, int V, const
                          float* logprob, uint8_t* greedy, const int64_t* spans, int R, double* span_sum, uint8_t* span_greedy,
                          int32_t* span_count, int32_t* status, void* stream);
 
+/* Prompt-lookup speculative decoding, the control plane (csrc/pbl_spec.hip; harness.DecodeSession.begin_speculation / harness.generate
+ * with prompt_lookup_num_tokens): a step feeds S = 1 + K tokens per row -- ids[b][0] the last emitted token, ids[b][1 .. S-1] drafts --
+ * and pbl_spec_verify_f16 closes it in two launches (one workgroup per row of logits for the arg-max, then one workgroup for the rest).
+ *   logits: fp16, row (b, s) at logits + b ld_b + s ld_s elements, unit stride inside a row, any alignment (the view
+ *   out.logits[:, -S:, :V] as it is); ids [B, S] int64; tokens [B, total] int64, the result; cursor, a DEVICE int64: the next column
+ *   of tokens to write, shared by all rows; unfinished, eos, n_eos, pad, n_unfinished, status: as in pbl_select_token_f16;
+ *   positions: a DEVICE table of L pointers to the layers' int64 cache positions (HF StaticLayer.cumulative_length), which the forward
+ *   pass has advanced by S; stats: PBL_SPEC_STATS_WORDS DEVICE int64 -- [0] steps, [1] drafts accepted and emitted, [2] tokens
+ *   emitted (only ever added to), [4 + b S + s] the arg-max of row (b, s) of the last call.
+ *     1. a[b][s] = the arg-max of row (b, s) by rule 5 of pbl_select_token_f16: the lowest index among the maxima, -0 equals +0, a
+ *        NaN counts as the maximum;
+ *     2. n_b = the largest n <= S - 1 with ids[b][j + 1] == a[b][j] for all j < n; n = the minimum of n_b over the rows whose
+ *        unfinished flag is set (the cache has ONE position for all rows; a row's further accepted drafts are discarded work);
+ *     3. w = min(n + 1, total - cursor) columns are written: tokens[b][cursor + j] = a[b][j], j < w; a row whose flag is clear
+ *        receives pad, a row whose token is an eos id clears its flag and receives pad from the next column on -- column by column
+ *        what w calls of pbl_select_token_f16 would have written; ids[b][0] = the row's last written token; cursor += w;
+ *        *n_unfinished = the flags still set; stats[0] += 1, stats[1] += w - 1, stats[2] += w;
+ *     4. every *positions[l] -= S - 1 - n: the valid cache rows are the last token's and the n accepted drafts'; the rows above the
+ *        position are never attended and the next append overwrites them;
+ *     5. cursor >= total, or no flag set: nothing is emitted (ids, tokens, cursor and stats[0 .. 3] stay), every *positions[l] -= S --
+ *        a surplus replay between two host polls is a no-op that cannot walk off the cache.  cursor outside [1, total]: the same,
+ *        and bit 1 of *status;
+ *     6. max_ngram >= 1 and S > 1, unless rule 5 applied: pbl_ngram_draft over the new history, in the second launch.
+ * pbl_ngram_draft fills ids[b][1 .. S-1] from the history h = tokens[b, :cursor] (cursor clamped to [0, total]): for N = max_ngram
+ * down to 1, an earlier occurrence of the last N tokens is h[e - N .. e) == h[len - N .. len) with N <= e < len; the first N that has
+ * one wins, and of its occurrences the latest (an integer maximum: deterministic).  The drafts are ext[e + j], j < S - 1, where ext is
+ * h followed by the drafts themselves (a self-overlapping copy, as in LZ77: a loop of period 1 or 2 drafts itself).  Without a match,
+ * and for rows whose unfinished flag is clear, every draft is ids[b][0], the row's last token.
+ * PBL_ERR_INVALID_ARG for NULL pointers (eos with n_eos = 0 and positions with L = 0 may be NULL), sizes < 1, ld_s < V with S > 1,
+ * rows of two batch entries that overlap, max_ngram outside [0, 4] ([1, 4] for pbl_ngram_draft) and outputs overlapping inputs or
+ * each other, before any device work; PBL_ERR_UNSUPPORTED for B S > 4, V > 524288 or total >= 2^31.  No workspace, no allocation, no
+ * synchronisation, nothing read on the host: capturable in a hipGraph, and one captured graph serves every step. */
+#define PBL_SPEC_STATS_WORDS 8
+int pbl_spec_verify_f16(const void* logits, int64_t ld_b, int64_t ld_s, int B, int S, int V, int64_t* ids, int64_t* tokens,
+                        int64_t total, int64_t* cursor, uint8_t* unfinished, const int64_t* eos, int n_eos, int64_t pad,
+                        int32_t* n_unfinished, int32_t* status, int64_t* const* positions, int L, int64_t* stats, int max_ngram,
+                        void* stream);
+int pbl_ngram_draft(const int64_t* tokens, int64_t total, int B, const int64_t* cursor, const uint8_t* unfinished, int64_t* ids, int S,
+                    int max_ngram, void* stream);
+
 /* ---------------- QAT step, weight side ------------------------------------------ */
 /* The elementwise work of one training step of BinaryXnorExceptOutliersLinear
  * (quant/outlier_quantizer.py:83-99; straight-through estimator quant/quantizer.py:18-25), fused into

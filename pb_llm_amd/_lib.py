@@ -20,6 +20,7 @@ PBL_FLAG_SAL_F16 = 0x2
 PBL_FLAG_TAIL_REPEAT = 0x4
 PBL_FLAG_SLABS = 0x8
 PBL_PACK_COUNT_WORDS = 56
+PBL_SPEC_STATS_WORDS = 8
 PBL_DTYPE_F32, PBL_DTYPE_F16, PBL_DTYPE_BF16 = 0, 1, 2
 (PBL_OK, PBL_ERR_INVALID_ARG, PBL_ERR_BAD_BLOB, PBL_ERR_UNSUPPORTED, PBL_ERR_MISALIGNED, PBL_ERR_CAPACITY, PBL_ERR_LAUNCH,
  PBL_ERR_NOT_REPRESENTABLE) = (0, -1, -2, -3, -4, -5, -6, -7)
@@ -62,7 +63,7 @@ EXPORTS = ["pbl_status_string", "pbl_version", "pbl_pack_dense_f32", "pbl_pack_d
            "pbl_gemm_f16_image_ws", "pbl_gemv_f16_fused_norm_host", "pbl_linear_f16_swiglu",
            "pbl_linear_f16_residual", "pbl_linear_f16_swiglu_residual", "pbl_rope_f16",
            "pbl_rope_append_f16", "pbl_decode_attn_workspace_bytes", "pbl_decode_attn_f16", "pbl_select_token_f16",
-           "pbl_score_tokens_f16", "pbl_gemv_route"]
+           "pbl_score_tokens_f16", "pbl_gemv_route", "pbl_spec_verify_f16", "pbl_ngram_draft"]
 
 
 def lib() -> C.CDLL:
@@ -244,6 +245,11 @@ def lib() -> C.CDLL:
                                        C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
     L.pbl_score_tokens_f16.restype = C.c_int
     L.pbl_score_tokens_f16.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.pbl_spec_verify_f16.restype = C.c_int
+    L.pbl_spec_verify_f16.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int64,
+                                      vp, vp, vp, C.c_int, vp, C.c_int, vp]
+    L.pbl_ngram_draft.restype = C.c_int
+    L.pbl_ngram_draft.argtypes = [vp, C.c_int64, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp]
     _lib = L
     return L
 

@@ -93,6 +93,29 @@ class _Selection:
     params: tuple[float, int, float]
 
 
+@dataclass
+class _Speculation:
+    """DecodeSession.begin_speculation's state: prompt in columns [0, col0) of `tokens`, K drafts per step from n-grams of at most
+    max_ngram tokens; `state` holds [cursor, unfinished count] as two int64 words (ONE device read per poll): `cursor` is a view of the
+    first, `count` an int32 view of the low half of the second"""
+    tokens: torch.Tensor
+    col0: int
+    total: int
+    K: int
+    max_ngram: int
+    pad: int
+    eos: torch.Tensor | None
+    ids: torch.Tensor
+    state: torch.Tensor
+    cursor: torch.Tensor
+    count: torch.Tensor
+    unfinished: torch.Tensor
+    status: torch.Tensor
+    stats: torch.Tensor
+    positions: torch.Tensor
+    polls: int = 0
+
+
 class DecodeSession:
     """Decoding state of `model` (a HF causal LM) for `batch` unpadded rows and at most `max_length` positions: a DecodeCache
     on the device and, with graph=True, ONE decode step captured in a hipGraph on its first call and replayed for every later
@@ -103,7 +126,10 @@ class DecodeSession:
     prefill / step hand the logits back and leave the choice of the token to the caller.  begin_selection / select / step_select
     keep the choice on the device as well (runtime.select_token_f16: greedy or temperature / top-k / top-p sampling, eos / pad
     bookkeeping): the captured unit is then "forward over static_ids, select into static_ids", and a generation is one replay per
-    token with nothing read on the host (run_selection reads the unfinished count every poll_every tokens)."""
+    token with nothing read on the host (run_selection reads the unfinished count every poll_every tokens).
+
+    begin_speculation / step_speculate / run_speculation decode greedily 1 + K tokens per row and step (prompt-lookup speculative
+    decoding): the unit is "forward over the last token and K drafts, verify, draft" (runtime.spec_verify_f16), captured once."""
 
     def __init__(self, model: nn.Module, batch: int, max_length: int, graph: bool = True):
         if batch < 1 or max_length < 1:
@@ -116,6 +142,7 @@ class DecodeSession:
         self._bool_mask = model.config._attn_implementation == "sdpa"
         self.static_ids = torch.zeros(self.batch, 1, dtype=torch.long, device=self.device)
         self.graph, self.static_logits, self.sel, self.sel_graph, self.pos = None, None, None, None, 0
+        self.spec, self.spec_graph = None, None
 
     def _mask(self, seq: int) -> torch.Tensor:
         """[batch, 1, seq, max_length]: query row s sees cache rows [0, position + s] (bool for SDPA, additive otherwise)"""
@@ -242,6 +269,119 @@ class DecodeSession:
             done = int(first.max())
         return c.tokens[:, :P + done]
 
+    # ---- prompt-lookup speculative decoding (greedy) on the device
+    @torch.no_grad()
+    def begin_speculation(self, prompt: torch.Tensor, total: int, draft_tokens: int = 3, max_ngram: int = 2, eos=(),
+                          pad: int | None = None, logits: torch.Tensor | None = None) -> torch.Tensor:
+        """Start a greedy generation that verifies draft_tokens = K drafted tokens per step (batch * (1 + K) <= 4 rows: one decode
+        launch): prefills `prompt` [batch, P < total] (unless `logits` are the logits of a prefill the caller has just run), chooses
+        the first token, drafts the first K from n-grams of at most max_ngram (1 .. 4) tokens of the row's own history, and returns the
+        result `tokens` [batch, total].  The session must hold K positions of slack: max_length >= total - 1 + K (a step appends
+        1 + K cache rows before the rejected ones are taken back).  eos / pad as in begin_selection."""
+        K, dev = int(draft_tokens), self.device
+        if prompt.dim() != 2 or prompt.shape[0] != self.batch or not prompt.shape[1] < total:
+            raise ValueError(f"DecodeSession.begin_speculation: prompt must be [{self.batch}, P < total]")
+        if K < 0 or not 1 <= max_ngram <= runtime.SPEC_MAX_NGRAM:
+            raise ValueError("DecodeSession.begin_speculation: draft_tokens >= 0 and max_ngram in 1 .. 4")
+        if self.max_length < total - 1 + K:
+            raise ValueError(f"DecodeSession.begin_speculation: max_length = {self.max_length} < total - 1 + draft_tokens = {total - 1 + K}")
+        if logits is None:
+            logits = self.prefill(prompt)
+        if logits.dtype != torch.float16 or not runtime.spec_verify_ok(self.batch, 1 + K, logits.shape[-1]):
+            raise ValueError("DecodeSession.begin_speculation: pbl_spec_verify_f16 declines these logits (runtime.spec_verify_ok)")
+        P = int(prompt.shape[1])
+        tokens = torch.zeros(self.batch, total, dtype=torch.long, device=dev)
+        tokens[:, :P] = prompt
+        eos = [int(e) for e in eos]
+        state = torch.tensor([P, self.batch], dtype=torch.long, device=dev)
+        c = self.spec = _Speculation(
+            tokens=tokens, col0=P, total=int(total), K=K, max_ngram=int(max_ngram), pad=0 if pad is None else int(pad),
+            eos=torch.tensor(eos, dtype=torch.long, device=dev) if eos else None,
+            ids=torch.zeros(self.batch, 1 + K, dtype=torch.long, device=dev), state=state, cursor=state[:1],
+            count=state[1:].view(torch.int32)[:1], unfinished=torch.ones(self.batch, dtype=torch.bool, device=dev),
+            status=torch.zeros(1, dtype=torch.int32, device=dev), stats=torch.zeros(8, dtype=torch.long, device=dev),
+            positions=torch.tensor([lay.cumulative_length.data_ptr() for lay in self.cache.layers], dtype=torch.long, device=dev))
+        self.spec_graph = None                                 # a captured unit holds the previous speculation's tensors
+        first = torch.zeros(self.batch, dtype=torch.long, device=dev)
+        if runtime.select_token_f16(logits, torch.zeros(1, dtype=torch.long, device=dev), c.unfinished, tokens, P, first, c.count,
+                                    c.status, eos=c.eos, pad=c.pad) is None:
+            raise ValueError("DecodeSession.begin_speculation: pbl_select_token_f16 declines these logits (runtime.select_token_ok)")
+        c.ids[:, 0] = first
+        c.cursor.fill_(P + 1)
+        if K and runtime.ngram_draft(tokens, c.cursor, c.unfinished, c.ids, c.max_ngram) is None:
+            raise ValueError("DecodeSession.begin_speculation: pbl_ngram_draft declines this shape")
+        return tokens
+
+    def _spec_unit(self):
+        c = self.spec
+        S = 1 + c.K
+        out = self.model(c.ids, attention_mask=self._mask(S), past_key_values=self.cache, use_cache=True, logits_to_keep=S)
+        if runtime.spec_verify_f16(out.logits[:, -S:], c.ids, c.tokens, c.cursor, c.unfinished, c.count, c.status, c.positions, c.stats,
+                                   eos=c.eos, pad=c.pad, max_ngram=c.max_ngram if c.K else 0) is None:
+            raise ValueError("DecodeSession.step_speculate: pbl_spec_verify_f16 declines these logits (runtime.spec_verify_ok)")
+
+    def _poll(self) -> tuple[int, int]:
+        """(cursor, unfinished rows): the one device read of the speculation loop; the host's position count becomes the truth"""
+        c = self.spec
+        cur, live = c.state.tolist()
+        c.polls += 1
+        self.pos = cur - 1                                     # every emitted token but the last is in the cache
+        return cur, live
+
+    @torch.no_grad()
+    def step_speculate(self, drafts: torch.Tensor | None = None) -> None:
+        """one speculative step over the last token and the K drafts in the unit's input: with graph=True ONE replay of a unit
+        captured on the first call.  drafts [batch, K]: the caller's drafts replace the n-gram ones for this step (another drafter).
+        Between polls the host counts 1 + K positions per step; before that count would refuse a step it reads the true one."""
+        c = self.spec
+        if drafts is not None:
+            if tuple(drafts.shape) != (self.batch, c.K):
+                raise ValueError(f"DecodeSession.step_speculate: drafts must be [{self.batch}, {c.K}]")
+            c.ids[:, 1:].copy_(drafts)
+        if self.pos + 1 + c.K > self.max_length:
+            self._poll()
+        self._advance(1 + c.K)
+        if not self.use_graph:
+            return self._spec_unit()
+        if self.spec_graph is None:
+            self.spec_graph, _ = self._capture(self._spec_unit, [c.ids, c.state, c.unfinished, c.status, c.stats, c.tokens])
+        self.spec_graph.replay()
+
+    @torch.no_grad()
+    def run_speculation(self, poll_every: int = 8) -> int:
+        """speculative steps until the result is full or every row has finished.  The host reads [cursor, unfinished rows] once per
+        poll; the next poll comes after as many steps as the remaining tokens need at full acceptance, ceil(remaining / (1 + K)) -- no
+        step runs after the last token -- and, with eos ids, after at most poll_every steps (steps after every row finished emit
+        nothing: the result does not depend on poll_every).  Returns the number of new tokens."""
+        c = self.spec
+        if poll_every < 1:
+            raise ValueError("DecodeSession.run_speculation: poll_every must be >= 1")
+        while True:
+            cur, live = self._poll()
+            if cur >= c.total or live == 0:
+                return cur - c.col0
+            need = -(-(c.total - cur) // (1 + c.K))
+            for _ in range(need if c.eos is None else min(poll_every, need)):
+                self.step_speculate()
+
+    def speculation_result(self) -> torch.Tensor:
+        """the prompt and the new tokens so far, cut after the column at which the last row finished (selection_result's rule)"""
+        c = self.spec
+        cur, _ = self._poll()
+        if int(c.status) & 2:
+            raise RuntimeError("generate: the speculation step ran outside the result buffer")
+        P, done = c.col0, cur - c.col0
+        if c.eos is not None and done:
+            hit = torch.isin(c.tokens[:, P:P + done], c.eos)
+            first = torch.where(hit.any(1), hit.int().argmax(1) + 1, done)
+            done = int(first.max())
+        return c.tokens[:, :P + done]
+
+    def speculation_stats(self) -> dict:
+        """steps run, drafts accepted and new tokens (the first one included): tokens == 1 + steps + accepted"""
+        steps, accepted, emitted = self.spec.stats[:3].tolist()
+        return dict(steps=steps, accepted=accepted, tokens=1 + emitted)
+
     def reset(self):
         """zero the cache rows and positions (the captured step stays valid: same tensors)"""
         self.cache.reset()
@@ -281,6 +421,7 @@ def _generation_limits(model: nn.Module, prompt_len: int, max_length=None, max_n
 
 _GREEDY_DEFAULTS = {"do_sample": False, "num_beams": 1, "use_cache": True}
 _SAMPLING_ARGS = ("temperature", "top_k", "top_p")
+_LOOKUP_ARGS = ("prompt_lookup_num_tokens", "max_matching_ngram_size")      # greedy only: prompt-lookup speculative decoding
 
 
 def _sampling_params(model: nn.Module, temperature=None, top_k=None, top_p=None) -> tuple[float, int, float]:
@@ -320,10 +461,17 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
     Handed to model.generate unchanged: an attention_mask with zeros (a padded batch), a model off the GPU, beams, any other
     generation argument (repetition_penalty, min_p, ...), do_sample=False together with sampling arguments, and sampling on a model
     whose logits are not fp16.  model.generate cannot honour `generator` or `uniforms`, so a call that passes one of them and must
-    be handed over raises ValueError.  Greedy decoding of logits that are not fp16 keeps the selection in torch."""
+    be handed over raises ValueError.  Greedy decoding of logits that are not fp16 keeps the selection in torch.
+
+    prompt_lookup_num_tokens (with max_matching_ngram_size, default 2, at most 4 here), greedy decoding only: prompt-lookup speculative
+    decoding on the device (DecodeSession.begin_speculation / run_speculation).  Each step feeds the last token and K =
+    min(prompt_lookup_num_tokens, 4 // B - 1) tokens drafted from the row's own history, and keeps the drafts that the greedy choice
+    confirms plus one more token: the greedy tokens, up to the effect of fp16 rounding on near-ties (a step of 1 + K rows and a step
+    of one row round differently).  K < 1, logits that are not fp16, a shape the entries decline or K slack positions that would pass
+    max_position_embeddings: the one-token loop above.  With do_sample=True the call is handed to model.generate."""
     sample = kwargs.get("do_sample", False) is True
     fixed = {k: v for k, v in _GREEDY_DEFAULTS.items() if not (sample and k == "do_sample")}
-    known = set(_GREEDY_DEFAULTS) | (set(_SAMPLING_ARGS) if sample else set())
+    known = set(_GREEDY_DEFAULTS) | set(_SAMPLING_ARGS if sample else _LOOKUP_ARGS)
     native = all(kwargs[k] == v for k, v in fixed.items() if k in kwargs) and not set(kwargs) - known
     padded = attention_mask is not None and not bool(attention_mask.all())
     T, top_k, top_p = 1.0, 0, 1.0                          # greedy: everything off
@@ -348,8 +496,21 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
         raise ValueError("generate: poll_every must be >= 1")
     B, P = input_ids.shape
     total, eos, pad = _generation_limits(model, P, max_length, max_new_tokens, eos_token_id, pad_token_id)
-    sess = DecodeSession(model, B, total - 1, graph=graph)
+    K = 0
+    if kwargs.get("prompt_lookup_num_tokens") is not None:
+        lookup, ngram = int(kwargs["prompt_lookup_num_tokens"]), int(kwargs.get("max_matching_ngram_size") or 2)
+        if lookup < 1 or ngram < 1:
+            raise ValueError("generate: prompt_lookup_num_tokens and max_matching_ngram_size must be >= 1")
+        K = max(0, min(lookup, runtime.SPEC_MAX_ROWS // B - 1))
+        cap = getattr(getattr(model, "config", None), "max_position_embeddings", None)
+        if model.get_input_embeddings().weight.dtype != torch.float16 or (cap is not None and total - 1 + K > cap):
+            K = 0
+    sess = DecodeSession(model, B, total - 1 + K, graph=graph)
     logits = sess.prefill(input_ids)
+    if K and logits.dtype == torch.float16 and runtime.spec_verify_ok(B, 1 + K, logits.shape[1]):
+        sess.begin_speculation(input_ids, total, draft_tokens=K, max_ngram=min(ngram, runtime.SPEC_MAX_NGRAM), eos=eos, pad=pad, logits=logits)
+        sess.run_speculation(poll_every)
+        return sess.speculation_result()
     if logits.dtype == torch.float16 and runtime.select_token_ok(B, logits.shape[1]):
         table = None
         if sample:

@@ -392,3 +392,90 @@ def score_tokens_f16(logits: torch.Tensor, targets: torch.Tensor, spans: torch.T
         return None
     _lib.check(rc, "token scoring")
     return logprob, greedy, span_sum, span_greedy, span_count, status
+
+
+SPEC_MAX_ROWS = _lib.PBL_MAX_TOKENS_PER_LAUNCH
+SPEC_MAX_NGRAM = 4
+
+
+def spec_verify_ok(batch: int, seq: int, vocab: int) -> bool:
+    """the scope of spec_verify_f16 (pbl_spec_verify_f16): the batch * seq <= 4 rows of one decode launch, select_token_f16's vocabulary"""
+    return batch >= 1 and seq >= 1 and batch * seq <= SPEC_MAX_ROWS and 1 <= vocab <= SELECT_MAX_VOCAB
+
+
+def _spec_state(what: str, ids: torch.Tensor, tokens: torch.Tensor, cursor: torch.Tensor, unfinished: torch.Tensor, dev) -> tuple[int, int]:
+    """(B, S) of the state spec_verify_f16 and ngram_draft share, after checking its form"""
+    def on(t, dtypes, n=None):
+        return t.is_cuda and t.device == dev and t.dtype in dtypes and t.is_contiguous() and (n is None or t.numel() == n)
+
+    if not on(ids, (torch.int64,)) or ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < 1:
+        raise ValueError(f"{what}: ids must be a contiguous int64 [B, S] GPU tensor")
+    B, S = (int(d) for d in ids.shape)
+    if not on(tokens, (torch.int64,)) or tokens.dim() != 2 or tokens.shape[0] != B or tokens.shape[1] < 1:
+        raise ValueError(f"{what}: tokens must be a contiguous int64 [B, total] tensor on the ids' device")
+    if not on(cursor, (torch.int64,), 1) or not on(unfinished, (torch.bool, torch.uint8), B):
+        raise ValueError(f"{what}: cursor (int64, one element) and unfinished (bool [B]) must be contiguous tensors on the ids' device")
+    return B, S
+
+
+def spec_verify_f16(logits: torch.Tensor, ids: torch.Tensor, tokens: torch.Tensor, cursor: torch.Tensor, unfinished: torch.Tensor,
+                    n_unfinished: torch.Tensor, status: torch.Tensor, positions: torch.Tensor, stats: torch.Tensor,
+                    eos: torch.Tensor | None = None, pad: int = 0, max_ngram: int = 0) -> bool | None:
+    """The end of a speculative decode step, on the device in one call (pbl_spec_verify_f16; the rules are in include/pbl.h): logits
+    [B, S, V] fp16 with unit stride inside a row (the view out.logits[:, -S:, :V] is fine, it is never copied) hold the step's rows
+    for ids [B, S] int64 -- column 0 the last emitted token, columns 1 .. S-1 the drafts.  The drafts are compared with the greedy
+    tokens of the rows before them; the prefix accepted by every unfinished row plus one bonus token go into tokens [B, total] from
+    column `cursor` (int64, one element; advanced), with select_token_f16's eos / pad bookkeeping (unfinished, n_unfinished, status,
+    eos, pad); ids[:, 0] becomes the last emitted token; the rejected rows are taken back from every position in `positions` (int64
+    [L]: the data_ptr() of each layer's int64 cache position); stats (int64 [PBL_SPEC_STATS_WORDS]) counts steps, accepted drafts
+    and tokens.  max_ngram >= 1: ngram_draft follows in the same call.  Nothing is read on the host and nothing allocated: capturable
+    in a hipGraph.  True when it ran, None where the entry declines (spec_verify_ok)."""
+    if not logits.is_cuda or logits.dim() != 3 or logits.dtype != torch.float16 or logits.stride(2) != 1 or min(logits.shape) < 1:
+        raise ValueError("spec_verify_f16: logits must be an fp16 [B, S, V] GPU tensor with unit stride inside a row")
+    dev = logits.device
+    B, S = _spec_state("spec_verify_f16", ids, tokens, cursor, unfinished, dev)
+    V = int(logits.shape[2])
+    if tuple(logits.shape[:2]) != (B, S) or (S > 1 and logits.stride(1) < V) or (B > 1 and logits.stride(0) < (S - 1) * logits.stride(1) + V):
+        raise ValueError("spec_verify_f16: logits must hold one row per element of ids [B, S], rows that do not overlap")
+
+    def on(t, dtype, n=None):
+        return t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and t.dim() <= 1 and (n is None or t.numel() == n)
+
+    if not on(n_unfinished, torch.int32, 1) or not on(status, torch.int32, 1) or not on(stats, torch.int64, _lib.PBL_SPEC_STATS_WORDS) \
+            or not on(positions, torch.int64):
+        raise ValueError("spec_verify_f16: n_unfinished and status (int32, one element), stats (int64 [8]) and positions (int64 [L]) "
+                         "must be contiguous tensors on the logits' device")
+    if eos is not None and not on(eos, torch.int64):
+        raise ValueError("spec_verify_f16: eos must be a 1-D int64 tensor on the logits' device")
+    if not 0 <= max_ngram <= SPEC_MAX_NGRAM:
+        raise ValueError("spec_verify_f16: max_ngram must be 0 (no drafting) .. 4")
+    if not spec_verify_ok(B, S, V) or tokens.shape[1] >= 1 << 31:
+        return None
+    n_eos, L = 0 if eos is None else int(eos.numel()), int(positions.numel())
+    rc = _lib.lib().pbl_spec_verify_f16(
+        logits.data_ptr(), logits.stride(0) if B > 1 else S * max(logits.stride(1), V), logits.stride(1) if S > 1 else V, B, S, V,
+        ids.data_ptr(), tokens.data_ptr(), int(tokens.shape[1]), cursor.data_ptr(), unfinished.data_ptr(),
+        eos.data_ptr() if n_eos else None, n_eos, int(pad), n_unfinished.data_ptr(), status.data_ptr(),
+        positions.data_ptr() if L else None, L, stats.data_ptr(), int(max_ngram), torch.cuda.current_stream(dev).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "speculation verify")
+    return True
+
+
+def ngram_draft(tokens: torch.Tensor, cursor: torch.Tensor, unfinished: torch.Tensor, ids: torch.Tensor, max_ngram: int = 2) -> bool | None:
+    """Prompt-lookup drafts (pbl_ngram_draft; the rules are in include/pbl.h): ids[b, 1:] of every row from the latest earlier
+    occurrence, in the row's history tokens[b, :cursor], of its last max_ngram .. 1 tokens (the longest length that has one); the
+    row's last token ids[b, 0] where nothing matches and for rows whose unfinished flag is clear.  All tensors on one GPU (the forms
+    of spec_verify_f16); nothing is read on the host.  True when it ran, None where the entry declines (more than 4 elements in ids)."""
+    B, S = _spec_state("ngram_draft", ids, tokens, cursor, unfinished, ids.device)
+    if not 1 <= max_ngram <= SPEC_MAX_NGRAM:
+        raise ValueError("ngram_draft: max_ngram must be 1 .. 4")
+    if B * S > SPEC_MAX_ROWS or tokens.shape[1] >= 1 << 31:
+        return None
+    rc = _lib.lib().pbl_ngram_draft(tokens.data_ptr(), int(tokens.shape[1]), B, cursor.data_ptr(), unfinished.data_ptr(), ids.data_ptr(), S,
+                                    int(max_ngram), torch.cuda.current_stream(ids.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "n-gram draft")
+    return True
