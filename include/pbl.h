@@ -543,6 +543,29 @@ int pbl_decode_attn_f16(const void* q, const int64_t* q_stride, const void* k_ca
                         int Hkv, int D, int max_len, float scaling, int64_t* pos, void* out, uint32_t ldo, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* Causal prefill attention over the same static KV cache (csrc/pbl_prefill.hip; fusion._folded_layer_forward with
+ * decoding.PREFILL_ATTENTION): S new rows per sequence, any S >= 1 and any B, at the device position p = *pos (never read on the host).
+ *   q [B, Hq, S, D], k_new / v_new [B, Hkv, S, D] fp16 with element strides {b, h, s} (host arrays of 3) and unit d stride: k_new is
+ *   rotated (pbl_rope_f16's k), v_new may be a strided view of the q/k/v output.
+ *   1. k_new / v_new are copied bit for bit into cache rows [p, p + S); rows at or beyond max_len are not written.
+ *   2. query row s of head h attends to cache rows [0, min(p + s, max_len - 1)] of kv head h / (Hq / Hkv): softmax(scaling q k^T) v.
+ *      Everything is read back from the cache: a second chunk at p > 0 goes the way the first went.  Rows at or beyond
+ *      min(p + S, max_len) are never used, whatever they hold (NaN included).
+ *   3. out [B S, ldo] fp16, row b S + s, head h at column h D (pbl_decode_attn_f16's layout).
+ *   4. *pos += S, by a one-thread launch after everything that reads it.
+ * Numerics: scores are fp32 sums of fp16 products on the matrix cores (v_mfma_f32_32x32x16_f16); the online softmax runs in fp32 over
+ * key tiles; P is rounded to fp16 for the P V product and the denominator is summed from the ROUNDED P; the accumulator is fp32 and
+ * acc / l is rounded to fp16 once.  Key tiles (64 rows) are laid from absolute key row 0 in every launch, so a query row's result
+ * depends only on its own q, its keys and that tiling -- not on which rows share its query tile, on S, or on how a prompt was
+ * chunked.  No atomics, fixed order: bit-stable from run to run, eager or replayed.
+ * PBL_ERR_INVALID_ARG before any device work for NULL pointers, sizes < 1, negative strides, ldo < Hq D, S > max_len, B Hkv max_len D
+ * > 2^40 and outputs (caches, out, pos) overlapping inputs or each other; PBL_ERR_MISALIGNED for caches that are not 16-B aligned;
+ * PBL_ERR_UNSUPPORTED unless D is 64 or 128, Hkv divides Hq and the grid fits (Hq, B <= 65535).  Three launches, no workspace, no
+ * allocation, no synchronisation: capturable in a hipGraph, and one graph serves every position. */
+int pbl_prefill_attn_f16(const void* q, const int64_t* q_stride, const void* k_new, const int64_t* k_stride, const void* v_new,
+                         const int64_t* v_stride, void* k_cache, void* v_cache, int B, int S, int Hq, int Hkv, int D, int max_len,
+                         float scaling, int64_t* pos, void* out, uint32_t ldo, void* stream);
+
 /* Token selection of a decode step (csrc/pbl_select.hip; harness.DecodeSession / harness.generate): temperature, top-k, top-p, the
  * draw and the eos / pad bookkeeping of a generation loop in one launch per step (B > 1: a second, one-wave launch that counts the
  * unfinished rows and advances the step).

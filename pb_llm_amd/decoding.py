@@ -13,7 +13,11 @@ from . import runtime
 # cache and attend through HF's StaticLayer.update and attention interface instead (tools/bench_generate.py compares the two).  Read
 # HERE when a step runs or is captured: nothing re-exports it.
 DECODE_ATTENTION = True
-_DECODE_CACHE = None                     # the DecodeCache class, made on first use (transformers is imported lazily)
+# The HIP causal prefill attention in folded layers for MORE than 4 rows over a DecodeCache (runtime.prefill_attention_f16).  False (the
+# default): those calls run LlamaDecoderLayer.forward -- StaticLayer.update and HF's attention interface over the whole cache
+# (tools/bench_prefill_attention.py compares the two).  Read HERE when a forward runs.
+PREFILL_ATTENTION = False
+_DECODE_CACHE = None                    # the DecodeCache class, made on first use (transformers is imported lazily)
 
 
 def _decode_cache_layer(cache, layer_idx: int, batch: int, n_kv: int, head_dim: int):
@@ -32,6 +36,23 @@ def _decode_cache_layer(cache, layer_idx: int, batch: int, n_kv: int, head_dim: 
     return lay
 
 
+def _prefill_cache_layer(cache, layer_idx: int, batch: int, seq: int, n_q: int, n_kv: int, head_dim: int):
+    """_decode_cache_layer's counterpart for the prefill-attention branch (any batch, any number of rows): cache is a DecodeCache, its
+    layer a plain, initialised StaticLayer of fp16 [batch, n_kv, max_len, head_dim] tensors that runtime.prefill_attention_ok takes
+    -- else None (HF's path)"""
+    if not PREFILL_ATTENTION or _DECODE_CACHE is None or not isinstance(cache, _DECODE_CACHE) or layer_idx is None \
+            or layer_idx >= len(cache.layers):
+        return None
+    from transformers.cache_utils import StaticLayer
+    lay = cache.layers[layer_idx]
+    if type(lay) is not StaticLayer or not lay.is_initialized or lay.keys.dtype != torch.float16:
+        return None
+    B, H, L, D = lay.keys.shape
+    if (B, H, D) != (batch, n_kv, head_dim) or not runtime.prefill_attention_ok(batch, seq, n_q, n_kv, head_dim, L):
+        return None
+    return lay
+
+
 def _decode_cache_class():
     global _DECODE_CACHE
     if _DECODE_CACHE is None:
@@ -43,7 +64,8 @@ def _decode_cache_class():
             that receives it treats it as a StaticCache: StaticLayer.update, prefill of more than 4 rows, unfolded layers and bf16
             models keep working.  A folded layer (fuse_decode_(epilogues=True)) whose cache layer is a plain fp16 StaticLayer
             appends to it and attends over its valid rows with the HIP decode attention (runtime.rope_append_f16 /
-            decode_attention_f16) instead; that path ignores the attention mask, hence the unpadded-batch contract."""
+            decode_attention_f16) instead -- and, with PREFILL_ATTENTION on, a prefill of more than 4 rows with
+            runtime.prefill_attention_f16; those paths ignore the attention mask, hence the unpadded-batch contract."""
 
             def __init__(self, config, batch: int, max_cache_len: int, device, dtype):
                 super().__init__(config=config, max_cache_len=max_cache_len)
@@ -164,7 +186,7 @@ class DecodeSession:
     @torch.no_grad()
     def prefill(self, ids: torch.Tensor) -> torch.Tensor:
         """ids [batch, S] at the current position, eagerly (<= 4 rows in folded layers: the HIP kernels; more: HF's StaticLayer.update
-        and attention).  Returns the last position's logits [batch, vocab]."""
+        and attention, or with PREFILL_ATTENTION the HIP prefill attention).  Returns the last position's logits [batch, vocab]."""
         if ids.dim() != 2 or ids.shape[0] != self.batch or ids.shape[1] < 1:
             raise ValueError(f"DecodeSession.prefill: ids must be [{self.batch}, S >= 1]")
         self._advance(ids.shape[1])

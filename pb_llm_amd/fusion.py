@@ -1,5 +1,6 @@
 """Decode-time fusion of HF LLaMA layers over packed linears (fuse_decode_; harness.py re-exports it): q/k/v and gate/up as ONE launch
-each, opt-in with norm / SwiGLU prologues and RoPE / residual epilogues.  Each fallback ladder is stated once: _FusedGroup._run, _mlp_tail."""
+each, opt-in with norm / SwiGLU prologues and RoPE / residual epilogues.  Each fallback ladder is stated once: _FusedGroup._run, _mlp_tail,
+_prefill_layer_forward."""
 from __future__ import annotations
 
 import logging
@@ -10,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import runtime
-from .decoding import _decode_cache_layer
+from .decoding import _decode_cache_layer, _prefill_cache_layer
 from .packing import concat_rows
 from .quant import PBLinear, tensor_version
 
@@ -223,15 +224,54 @@ def _mlp_tail(down: PBLinear, act_fn, gu: torch.Tensor, inter: int, residual: to
     return y if residual is None else residual + y.reshape(residual.shape)
 
 
+def _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings):
+    """THE prefill-attention ladder of a folded layer (decoding.PREFILL_ATTENTION): more than 4 fp16 rows on the GPU without autograd,
+    position_embeddings given, the layer not training and a DecodeCache layer that runtime.prefill_attention_ok takes -- else None,
+    before anything ran, and the caller runs LlamaDecoderLayer.forward.  The layer as LlamaDecoderLayer / LlamaAttention compute it:
+    the input norm, q / k / v through their modules (the GEMM kernels, as without the switch), RoPE in one launch (runtime.rope_f16,
+    else HF's apply_rotary_pos_emb), the cache append and the causal attention over the valid rows (runtime.prefill_attention_f16,
+    which advances the layer's position on the device as StaticLayer.update would have), o_proj, the residual, the post norm, the
+    MLP and the residual.  The attention mask is not used: DecodeCache's unpadded-batch contract."""
+    x = hidden_states
+    attn = self.self_attn
+    if position_embeddings is None or x.dim() != 3 or x.shape[0] * x.shape[1] <= 4 or not x.is_cuda or x.dtype != torch.float16 \
+            or (torch.is_grad_enabled() and x.requires_grad) or self.training or attn.training:
+        return None
+    B, S, _ = x.shape
+    D = attn.head_dim
+    n_q, n_kv = attn.q_proj.out_features // D, attn.k_proj.out_features // D
+    lay = _prefill_cache_layer(past_key_values, attn.layer_idx, B, S, n_q, n_kv, D)
+    if lay is None:
+        return None
+    from transformers.models.llama import modeling_llama as ML
+    cos, sin = position_embeddings
+    xn = self.input_layernorm(x)
+    qk = torch.cat((attn.q_proj(xn).reshape(B * S, n_q * D), attn.k_proj(xn).reshape(B * S, n_kv * D)), dim=1)
+    v = attn.v_proj(xn).view(B, S, n_kv, D).transpose(1, 2)
+    rot = runtime.rope_f16(qk, 0, n_q * D, B, S, n_q, n_kv, D, cos, sin)
+    if rot is None:
+        rot = ML.apply_rotary_pos_emb(qk[:, :n_q * D].view(B, S, n_q, D).transpose(1, 2),
+                                      qk[:, n_q * D:].view(B, S, n_kv, D).transpose(1, 2), cos, sin)
+    a = runtime.prefill_attention_f16(rot[0], rot[1], v, lay.keys, lay.values, lay.cumulative_length, attn.scaling)
+    if a is None:                           # (prefill_attention_ok held for the cache layer)
+        raise RuntimeError("prefill_attention_f16 declined a shape prefill_attention_ok took")
+    h1 = x + attn.o_proj(a.view(B, S, -1))
+    return h1 + self.mlp(self.post_attention_layernorm(h1))
+
+
 def _folded_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
                           position_embeddings=None, **kwargs):
     """LlamaDecoderLayer.forward of a layer folded by fuse_decode_(epilogues=True), installed on the instance.  At <= 4 fp16 rows
     without autograd, with position_embeddings given: the q/k/v launch (RMSNorm prologue), ONE RoPE launch (runtime.rope_f16),
     HF's cache update and attention interface, o_proj with the residual add in its store, the gate/up launch (RMSNorm prologue) and
     down_proj with the SwiGLU prologue and the residual add -- every step with HF's roundings, so the result equals the
-    prologues=True layer's bit for bit.  Every other call runs LlamaDecoderLayer.forward (the prologues=True layer)."""
+    prologues=True layer's bit for bit.  More than 4 rows with decoding.PREFILL_ATTENTION on: _prefill_layer_forward (the HIP causal prefill attention over
+    a DecodeCache).  Every other call runs LlamaDecoderLayer.forward (the prologues=True layer)."""
     d_in = self.input_layernorm
     if position_embeddings is None or hidden_states.dim() != 3 or not _prologue_ok(hidden_states, d_in.norm.weight, stateless=True):
+        out = _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings)
+        if out is not None:
+            return out
         return type(self).forward(self, hidden_states, attention_mask=attention_mask, position_ids=position_ids,
                                   past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings, **kwargs)
     from transformers.models.llama import modeling_llama as ML

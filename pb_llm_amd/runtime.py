@@ -288,6 +288,40 @@ def decode_attention_f16(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
     return out
 
 
+def prefill_attention_ok(batch: int, seq: int, n_q: int, n_kv: int, head_dim: int, max_len: int) -> bool:
+    """the scope of prefill_attention_f16 (pbl_prefill_attn_f16): any batch and any seq >= 1 that fits the cache, head_dim 64 or 128,
+    n_kv dividing n_q, a grid that fits and a cache of at most 2^40 elements"""
+    return head_dim in (64, 128) and 1 <= batch <= 65535 and 1 <= seq <= max_len and n_kv >= 1 and 1 <= n_q <= 65535 \
+        and n_q % n_kv == 0 and batch * n_kv * max_len * head_dim <= 1 << 40
+
+
+def prefill_attention_f16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                          pos: torch.Tensor, scaling: float) -> torch.Tensor | None:
+    """Causal attention of S new rows over a static KV cache (pbl_prefill_attn_f16): q [B, Hq, S, D], k / v [B, Hkv, S, D] fp16 with
+    unit d stride (rope_f16's q and k; v a strided view of the q/k/v output), k_cache / v_cache [B, Hkv, max_len, D] fp16, pos the
+    int64 device position.  Appends k / v to cache rows [pos, pos + S), lets query row s attend to cache rows [0, pos + s], returns
+    [B * S, Hq * D] fp16 (what LlamaAttention hands o_proj) and advances pos by S on the device.  None where the entry declines
+    (prefill_attention_ok); the cache and pos are then untouched."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 4 or t.dtype != torch.float16 or not t.is_cuda or t.device != q.device or t.stride(3) != 1 or min(t.stride()) < 0:
+            raise ValueError(f"prefill_attention_f16: {name} must be an fp16 [B, H, S, D] GPU tensor with unit d stride")
+    B, Hq, S, D = (int(d) for d in q.shape)
+    Bc, Hkv, max_len, Dc = _cache_args(k_cache, v_cache, pos, q.device, "prefill_attention_f16")
+    if (Bc, Dc) != (B, D) or tuple(k.shape) != (B, Hkv, S, D) or k.shape != v.shape:
+        raise ValueError("prefill_attention_f16: k / v must be [B, Hkv, S, D] and the cache [B, Hkv, max_len, D] for q [B, Hq, S, D]")
+    if not prefill_attention_ok(B, S, Hq, Hkv, D, max_len):
+        return None
+    out = torch.empty(B * S, Hq * D, dtype=torch.float16, device=q.device)
+    rc = _lib.lib().pbl_prefill_attn_f16(q.data_ptr(), (C.c_int64 * 3)(*q.stride()[:3]), k.data_ptr(), (C.c_int64 * 3)(*k.stride()[:3]),
+                                         v.data_ptr(), (C.c_int64 * 3)(*v.stride()[:3]), k_cache.data_ptr(), v_cache.data_ptr(), B, S,
+                                         Hq, Hkv, D, max_len, float(scaling), pos.data_ptr(), out.data_ptr(), Hq * D,
+                                         torch.cuda.current_stream(q.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "prefill attention")
+    return out
+
+
 SELECT_MAX_VOCAB = 1 << 19
 
 
