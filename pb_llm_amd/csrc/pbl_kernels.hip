@@ -29,28 +29,8 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 #define PBL_WAVE 64
-// Ablation builds for performance analysis only (tools/ablate.sh): 1 = memory only
-// (loads kept live, math skipped), 2 = compute only (weight-stream loads skipped).
-// TIMING-ONLY probes for tools/build_variant.sh (results are wrong; 0 in every shipped build): bit 0 chunk partials at half size
-// (one more workgroup per CU), 1 no per-word sum of x, 2 classes 8 / 9 unpacked by a plain AND, 3 tile loads without nt,
-// 4 salient loads without nt
-#ifndef PBL_PROBE
-#define PBL_PROBE 0
-#endif
-#ifndef PBL_ABLATE
-#define PBL_ABLATE 0
-#endif
-// pbl_unpack_dev: stream the dense rows out with non-temporal stores (A/B builds; the library GEMM that follows reads the
-// buffer right away, so bypassing the caches is not obviously right)
-#ifndef PBL_UNPACK_NT
-#define PBL_UNPACK_NT 0
-#endif
 
 namespace {
-
-typedef uint32_t probe_u32x4 __attribute__((ext_vector_type(4)));
-template <typename T> __device__ __forceinline__ T load_tile(const T* p) { return (PBL_PROBE & 8) ? *p : __builtin_nontemporal_load(p); }
-template <typename T> __device__ __forceinline__ T load_sal(const T* p) { return (PBL_PROBE & 16) ? *p : __builtin_nontemporal_load(p); }
 
 __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {
     return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, a), __builtin_bit_cast(h2, b), c, false);
@@ -93,7 +73,7 @@ __device__ __forceinline__ void class_consts(int ci, float& A, float& B) {
 // literal on gfx9; with M in an SGPR and C in a VGPR it is a single v_and_or_b32.
 template <int CI>
 __device__ __forceinline__ uint32_t unpack_pair(uint32_t w, uint32_t c_one, float order_after) {
-    if constexpr (BitClass<CI>::C == 0u || ((PBL_PROBE & 4) && CI < 2)) {
+    if constexpr (BitClass<CI>::C == 0u) {
         return w & BitClass<CI>::M;
     } else {
         // `order_after` (an accumulator the previous class step wrote) is an unused input: it pins this instruction behind that
@@ -122,9 +102,8 @@ template <int MB>
 __device__ __forceinline__ void word_step(uint32_t w, uint32_t c_one, const uint32_t (&xr)[MB],
                                           float (&acc)[MB][16], float (&xl)[MB]) {
     const uint32_t ws = w << 8;
-    if (!(PBL_PROBE & 2))
 #pragma unroll
-        for (int m = 0; m < MB; ++m) xl[m] = dot2(c_one, xr[m], xl[m]);
+    for (int m = 0; m < MB; ++m) xl[m] = dot2(c_one, xr[m], xl[m]);
     class_step<MB, 0>(w, ws, c_one, xr, acc);
     class_step<MB, 1>(w, ws, c_one, xr, acc);
     class_step<MB, 2>(w, ws, c_one, xr, acc);
@@ -314,20 +293,6 @@ __device__ __forceinline__ void chunk_accumulate(uint32_t xbase, uint32_t tok_st
     }
 }
 
-#ifndef PBL_TILE_RING
-#define PBL_TILE_RING 2          // 2: rotating tile registers (63 VGPRs, 8 waves/SIMD; hipcc waits vmcnt(0) at the rotation, so
-                                 // the lookahead is one panel).  3: static three-set ring, a true two-panel lookahead at 74 VGPRs
-                                 // = 6 waves/SIMD.  Measured equal on the driver command (round 3, profiles/r03_gemv_ring.md):
-                                 // 0.669-0.688 of the HBM roofline for 3 vs 0.663-0.680 for 2 -- kept selectable, default unchanged.
-#endif
-#ifndef PBL_MIN_WAVES
-#define PBL_MIN_WAVES 1
-#endif
-// SPLIT == 1: each of the WPB waves of a workgroup owns its own record (throughput mode, the
-// L-layer stream).  SPLIT > 1 (== WPB): the waves of a workgroup COOPERATE on one record --
-// wave w takes panels w, w+S, ... and salient rounds w, w+S, ... and the partial sums are
-// merged through LDS -- so one small layer (256 records at N = 4096) still puts thousands of
-// waves on the chip (latency mode, sequential decode).
 // fp32 -> bf16 bits, round to nearest even; NaN stays NaN (csrc/pbl_act.hip)
 __device__ __forceinline__ uint32_t bf16_bits_rne(float f) {
     const uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -363,12 +328,38 @@ __device__ __forceinline__ uint32_t rmsnorm_f16(uint32_t xb, uint32_t gb, float 
     return uint32_t(__builtin_bit_cast(uint16_t, o));
 }
 
+// Phase 0's copy of one token: dst[i] = f(a[i], b[i]) for i < K, then zeroes in [K, xstride).  f maps fp16 / bf16 bit patterns to
+// fp16 bits; b is the transform's second operand (the norm's weight, SwiGLU's up; a itself where there is none).  vec (the caller's
+// test: K % 8 == 0 and every source 16-byte aligned): 8 halves per lane and step; else one.
+template <int NTHR, typename F>
+__device__ __forceinline__ void stage_row(_Float16* dst, const uint16_t* a, const uint16_t* b, int K, int xstride, bool vec, int tid, F f) {
+    if (vec) {
+        const u32x4* asrc = reinterpret_cast<const u32x4*>(a);
+        const u32x4* bsrc = reinterpret_cast<const u32x4*>(b);
+        for (int i = tid; i < (K >> 3); i += NTHR) {
+            const u32x4 v = asrc[i], w = bsrc[i];
+            u32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = f(v[j] & 0xFFFFu, w[j] & 0xFFFFu) | (f(v[j] >> 16, w[j] >> 16) << 16);
+            reinterpret_cast<u32x4*>(dst)[i] = o;
+        }
+    } else {
+        for (int i = tid; i < K; i += NTHR) reinterpret_cast<uint16_t*>(dst)[i] = uint16_t(f(a[i], b[i]));
+    }
+    for (int i = K + tid; i < xstride; i += NTHR) dst[i] = _Float16(0);
+}
+
+// SPLIT == 1: each of the WPB waves of a workgroup owns its own record (throughput mode, the
+// L-layer stream).  SPLIT > 1 (== WPB): the waves of a workgroup COOPERATE on one record --
+// wave w takes panels w, w+S, ... and salient rounds w, w+S, ... and the partial sums are
+// merged through LDS -- so one small layer (256 records at N = 4096) still puts thousands of
+// waves on the chip (latency mode, sequential decode).
 // XB: bf16 activations converted in the staging phase, bf16 result (GemvArgs.x_bf16).  A template parameter, not a run-time branch:
 // the fp16 instantiations -- the headline kernel among them -- are the code they were.  XP (x prologue, fp16 only): XP_RMSNORM stages
 // LlamaRMSNorm(x) (pass 1: every token's sum of squares, one barrier, pass 2: the normalised row), XP_SWIGLU stages silu(gate) * up.
 // XE_RESIDUAL (or-ed in) adds the residual in the store: fp16 result, then the fp16 add.
 template <int MB, int WPB, bool SF, int SPLIT, bool XB = false, int XP = XP_NONE>
-__global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void pbl_gemv_kernel(GemvArgs args) {
+__global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs args) {
     static_assert(SPLIT == 1 || SPLIT == WPB, "split mode uses every wave of the workgroup on one record");
     static_assert(!(XB && XP != XP_NONE), "the x prologues and the residual epilogue take fp16 activations");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -441,26 +432,20 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
     const u32x4* codep = reinterpret_cast<const u32x4*>(sal + PBL_SAL_CODE_OFF(nchu));
     const uint8_t* tailcnt = sal + PBL_SAL_TAILCNT_OFF(nchu);
 
-    // Three tile registers sets, statically indexed: a set is re-requested for the panel three steps on right after its last
-    // use, so a request has two whole panels of arithmetic to land.  (Rounds 1-2 rotated t0 <- t1 <- t2: the copy touches the
-    // register of a load issued at the top of the same iteration, hipcc waits vmcnt(0) in front of it, and the "two panels
-    // ahead" prefetch was in fact one panel deep -- 1 KiB per wave in flight.)
-    u32x4 t0 = {0, 0, 0, 0}, t1 = {0, 0, 0, 0}, t2 = {0, 0, 0, 0};
-    (void)t2;                   // (only the three-set ring uses it)
+    // Two tile registers, rotated in phase 1 (t0 <- t1 <- the panel two steps on), and this wave's first salient round.  The
+    // weight stream is read once: every load of it is non-temporal.
+    u32x4 t0 = {0, 0, 0, 0}, t1 = {0, 0, 0, 0};
     uint32_t s_c0 = 0;
     u32x4 s_d4 = {0, 0, 0, 0}, s_q4 = {0, 0, 0, 0};
-    uint32_t abl = 0;
-    (void)abl;
-    if (active && PBL_ABLATE != 2) {
-        if (wslot < P) t0 = load_tile(tiles + wslot * 64);
-        if (wslot + WSTEP < P) t1 = load_tile(tiles + (wslot + WSTEP) * 64);
-        if (PBL_TILE_RING == 3 && wslot + 2 * WSTEP < P) t2 = load_tile(tiles + (wslot + 2 * WSTEP) * 64);
+    if (active) {
+        if (wslot < P) t0 = __builtin_nontemporal_load(tiles + wslot * 64);
+        if (wslot + WSTEP < P) t1 = __builtin_nontemporal_load(tiles + (wslot + WSTEP) * 64);
         if (nch > wslot * PBL_WAVE) {
             const int c_first = wslot * PBL_WAVE + lane;
             const int cc = c_first < nch ? c_first : nch - 1;
             s_c0 = col0p[cc];
-            s_d4 = load_sal(deltap + cc);
-            s_q4 = load_sal(codep + cc);
+            s_d4 = __builtin_nontemporal_load(deltap + cc);
+            s_q4 = __builtin_nontemporal_load(codep + cc);
         }
     }
 
@@ -509,22 +494,8 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
             const int e = eb > 0 ? eb : 0;
             const float down = __builtin_bit_cast(float, uint32_t(127 - e) << 23);
             if (tid == 0) s_tscale[m] = finite ? __builtin_bit_cast(float, uint32_t(127 + e) << 23) : __builtin_inff();
-            if (vec) {
-                const u32x4* src = reinterpret_cast<const u32x4*>(xb + size_t(m) * K);
-                u32x4* dst = reinterpret_cast<u32x4*>(xs + m * xstride);
-                for (int i = tid; i < (K >> 3); i += nthr) {
-                    const u32x4 v = src[i];
-                    u32x4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        o[j] = bf16_to_scaled_f16(v[j] & 0xFFFFu, finite, down) | (bf16_to_scaled_f16(v[j] >> 16, finite, down) << 16);
-                    dst[i] = o;
-                }
-            } else {
-                for (int i = tid; i < K; i += nthr)
-                    reinterpret_cast<uint16_t*>(xs)[m * xstride + i] = uint16_t(bf16_to_scaled_f16(xb[size_t(m) * K + i], finite, down));
-            }
-            for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
+            stage_row<nthr>(xs + m * xstride, xb + size_t(m) * K, xb + size_t(m) * K, K, xstride, vec, tid,
+                            [&](uint32_t v, uint32_t) { return bf16_to_scaled_f16(v, finite, down); });
         }
     } else if constexpr ((XP & 3) == XP_RMSNORM) {
         // LlamaRMSNorm.forward on an fp16 row: pass 1 sums x^2 in fp32 (x^2 of an fp16 value is exact), one partial per (token, wave),
@@ -565,23 +536,8 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
 #pragma unroll
             for (int w = 0; w < WPB; ++w) ss += s_ssq[m * WPB + w];
             const float r = 1.0f / sqrtf(ss * (1.0f / float(K)) + args.norm_eps);
-            if (vec) {
-                const u32x4* src = reinterpret_cast<const u32x4*>(xb + size_t(m) * K);
-                const u32x4* gsrc = reinterpret_cast<const u32x4*>(gw);
-                u32x4* dst = reinterpret_cast<u32x4*>(xs + m * xstride);
-                for (int i = tid; i < (K >> 3); i += nthr) {
-                    const u32x4 v = src[i], g = gsrc[i];
-                    u32x4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        o[j] = rmsnorm_f16(v[j] & 0xFFFFu, g[j] & 0xFFFFu, r) | (rmsnorm_f16(v[j] >> 16, g[j] >> 16, r) << 16);
-                    dst[i] = o;
-                }
-            } else {
-                for (int i = tid; i < K; i += nthr)
-                    reinterpret_cast<uint16_t*>(xs)[m * xstride + i] = uint16_t(rmsnorm_f16(xb[size_t(m) * K + i], gw[i], r));
-            }
-            for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
+            stage_row<nthr>(xs + m * xstride, xb + size_t(m) * K, gw, K, xstride, vec, tid,
+                            [&](uint32_t v, uint32_t g) { return rmsnorm_f16(v, g, r); });
         }
     } else if constexpr ((XP & 3) == XP_SWIGLU) {
         // silu(gate) * up from the fused gate/up launch's output: row m holds gate at [0, K) and up at [up_off, up_off + K)
@@ -590,45 +546,20 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
         const size_t ldx = args.ldx;
         const uint32_t uo = args.up_off;
         const bool vec = (K & 7) == 0 && (reinterpret_cast<uintptr_t>(xb) & 15) == 0 && (ldx & 7) == 0 && (uo & 7) == 0;
-        for (int m = 0; m < MB; ++m) {
-            if (vec) {
-                const u32x4* gsrc = reinterpret_cast<const u32x4*>(xb + size_t(m) * ldx);
-                const u32x4* usrc = reinterpret_cast<const u32x4*>(xb + size_t(m) * ldx + uo);
-                u32x4* dst = reinterpret_cast<u32x4*>(xs + m * xstride);
-                for (int i = tid; i < (K >> 3); i += nthr) {
-                    const u32x4 g = gsrc[i], u = usrc[i];
-                    u32x4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        o[j] = swiglu_f16(g[j] & 0xFFFFu, u[j] & 0xFFFFu) | (swiglu_f16(g[j] >> 16, u[j] >> 16) << 16);
-                    dst[i] = o;
-                }
-            } else {
-                for (int i = tid; i < K; i += nthr)
-                    reinterpret_cast<uint16_t*>(xs)[m * xstride + i] = uint16_t(swiglu_f16(xb[size_t(m) * ldx + i], xb[size_t(m) * ldx + uo + i]));
-            }
-            for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
-        }
+        for (int m = 0; m < MB; ++m)
+            stage_row<nthr>(xs + m * xstride, xb + size_t(m) * ldx, xb + size_t(m) * ldx + uo, K, xstride, vec, tid, swiglu_f16);
     } else {
         const int nthr = WPB * PBL_WAVE;
-        if ((K & 7) == 0 && (reinterpret_cast<uintptr_t>(xg) & 15) == 0) {
-            const int nv = K >> 3;
-            for (int m = 0; m < MB; ++m) {
-                const u32x4* src = reinterpret_cast<const u32x4*>(xg + size_t(m) * K);
-                u32x4* dst = reinterpret_cast<u32x4*>(xs + m * xstride);
-                for (int i = tid; i < nv; i += nthr) dst[i] = src[i];
-            }
-        } else {
-            for (int m = 0; m < MB; ++m)
-                for (int i = tid; i < K; i += nthr) xs[m * xstride + i] = xg[size_t(m) * K + i];
-        }
+        const uint16_t* xb = reinterpret_cast<const uint16_t*>(xg);
+        const bool vec = (K & 7) == 0 && (reinterpret_cast<uintptr_t>(xb) & 15) == 0;
         for (int m = 0; m < MB; ++m)
-            for (int i = K + tid; i < xstride; i += nthr) xs[m * xstride + i] = _Float16(0);
+            stage_row<nthr>(xs + m * xstride, xb + size_t(m) * K, xb + size_t(m) * K, K, xstride, vec, tid,
+                            [](uint32_t v, uint32_t) { return v; });
     }
     __syncthreads();
     if (!active) return;  // no barriers below this point
 
-    // ---- phase 1: sign plane (tile loads run two panels ahead) ------------------------
+    // ---- phase 1: sign plane ----------------------------------------------------------
     float acc[MB][16];
     float xl[MB];
 #pragma unroll
@@ -647,35 +578,19 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
             uint32_t xr[MB];
 #pragma unroll
             for (int m = 0; m < MB; ++m) xr[m] = xw[(m * xstride) / 2 + i * 64];
-            if (PBL_ABLATE == 1) { abl ^= t[i] ^ xr[0]; continue; }
-            word_step<MB>(t[i] ^ (PBL_ABLATE == 2 ? uint32_t(p * 4 + i + lane) : 0u), c_one, xr, acc, xl);
+            word_step<MB>(t[i], c_one, xr, acc, xl);
         }
     };
-#if PBL_TILE_RING == 3
-    for (int p = wslot; p < P; p += 3 * WSTEP) {
-        panel(t0, p);
-        if (p + 3 * WSTEP < P && PBL_ABLATE != 2) t0 = load_tile(tiles + (p + 3 * WSTEP) * 64);
-        asm volatile("" ::: "memory");       // (keeps the next panel's LDS reads of x from being hoisted: 80 -> 64 VGPRs)
-        if (p + WSTEP < P) {
-            panel(t1, p + WSTEP);
-            if (p + 4 * WSTEP < P && PBL_ABLATE != 2) t1 = load_tile(tiles + (p + 4 * WSTEP) * 64);
-        }
-        asm volatile("" ::: "memory");
-        if (p + 2 * WSTEP < P) {
-            panel(t2, p + 2 * WSTEP);
-            if (p + 5 * WSTEP < P && PBL_ABLATE != 2) t2 = load_tile(tiles + (p + 5 * WSTEP) * 64);
-        }
-        asm volatile("" ::: "memory");
-    }
-#else
-    for (int p = wslot; p < P; p += WSTEP) {              // the rotating form of rounds 1-2 (kept for A/B runs)
+    // The load for panel p + 2 is requested before panel p's arithmetic; the rotation below copies into the register of that load,
+    // hipcc waits vmcnt(0) in front of the copy, and so the prefetch is one panel deep (1 KiB per wave in flight).  A static
+    // three-set ring with a true two-panel lookahead measured equal at 6 instead of 8 waves per SIMD (profiles/r03_gemv_ring.md).
+    for (int p = wslot; p < P; p += WSTEP) {
         u32x4 tn = t1;
-        if (p + 2 * WSTEP < P && PBL_ABLATE != 2) tn = load_tile(tiles + (p + 2 * WSTEP) * 64);
+        if (p + 2 * WSTEP < P) tn = __builtin_nontemporal_load(tiles + (p + 2 * WSTEP) * 64);
         panel(t0, p);
         t0 = t1;
         t1 = tn;
     }
-#endif
 
     // reduce the 16 row accumulators now: from here on one register per token carries the
     // binary result (lane l holds row rho(l), see transpose_reduce16)
@@ -697,7 +612,7 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
     const bool has_crow = L.flags & (PBL_FLAG_HAS_GROUPS | PBL_FLAG_SAL_F16);
 
     // ---- phase 2: salient chunks (next round's loads issued before this round's math) ---
-    float2* part = part_all + (SPLIT > 1 ? size_t(0) : size_t(wave) * ((PBL_PROBE & 1) ? (L.max_nch + 1) / 2 : L.max_nch) * MB);
+    float2* part = part_all + (SPLIT > 1 ? size_t(0) : size_t(wave) * L.max_nch * MB);
     {
         const uint32_t xbase = uint32_t(reinterpret_cast<uintptr_t>(xs));      // LDS byte offset of x
         const uint32_t tok_stride = uint32_t(xstride) * 2u;
@@ -708,11 +623,11 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
             const int cc = valid ? c : nch - 1;
             const uint32_t c0 = s_c0;
             const u32x4 d4 = s_d4, q4 = s_q4;
-            if (base + WSTEP * PBL_WAVE < nch && PBL_ABLATE != 2) {
+            if (base + WSTEP * PBL_WAVE < nch) {
                 const int cn = c + WSTEP * PBL_WAVE < nch ? c + WSTEP * PBL_WAVE : nch - 1;
                 s_c0 = col0p[cn];
-                s_d4 = load_sal(deltap + cn);
-                s_q4 = load_sal(codep + cn);
+                s_d4 = __builtin_nontemporal_load(deltap + cn);
+                s_q4 = __builtin_nontemporal_load(codep + cn);
             }
             float Q[MB], S[MB];
 #pragma unroll
@@ -722,9 +637,7 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
                 if (cc >= nfull) cnt = tailcnt[cc - nfull];
                 if (!valid) cnt = 0;
             }
-            if (PBL_ABLATE == 1) {
-                abl ^= c0 ^ d4[0] ^ d4[1] ^ d4[2] ^ d4[3] ^ q4[0] ^ q4[1] ^ q4[2] ^ q4[3];
-            } else if (SF && sf) {
+            if (SF && sf) {
                 // this chunk's row -> its (scale, zero) from the row-owner lane (no memory round trip)
                 const int crw = crow[cc];
                 const int owner = ((crw & 8) << 2) | ((crw & 4) << 2) | ((crw & 2) << 2) | ((crw & 1) << 2);
@@ -741,7 +654,7 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
             if (valid) {
 #pragma unroll
                 for (int m = 0; m < MB; ++m)   // code mode: undo the 1024 code bias here, once per chunk
-                    part[size_t(m) * L.max_nch + ((PBL_PROBE & 1) ? (c >> 1) : c)] = make_float2((SF && sf) ? Q[m] : fmaf(-1024.f, S[m], Q[m]), S[m]);
+                    part[size_t(m) * L.max_nch + c] = make_float2((SF && sf) ? Q[m] : fmaf(-1024.f, S[m], Q[m]), S[m]);
             }
         }
     }
@@ -782,11 +695,11 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
         float Q = 0.f, S = 0.f;
         const float2* pm = part + size_t(m) * L.max_nch;
         for (int k = sub; k < int(ri.nfull); k += 4) {
-            const float2 v = pm[(PBL_PROBE & 1) ? ((ri.start + k) >> 1) : (ri.start + k)];
+            const float2 v = pm[ri.start + k];
             Q += v.x; S += v.y;
         }
         for (int k = sub; k < int(ri.ntail); k += 4) {
-            const float2 v = pm[(PBL_PROBE & 1) ? ((nfull + ri.tailidx + k) >> 1) : (nfull + ri.tailidx + k)];
+            const float2 v = pm[nfull + ri.tailidx + k];
             Q += v.x; S += v.y;
         }
         Q = quad_sum(Q); S = quad_sum(S);
@@ -804,7 +717,6 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
             const float bv = (L.bias && row < L.N) ? L.bias[row] : 0.f;
             yv = fmaf(yv, s_tscale[m], bv);
         } else if (L.bias && row < L.N) yv += L.bias[row];
-        if (PBL_ABLATE == 1 && abl == 0x9E3779B9u) yv += 1.f;
         if (sub == 0 && row < L.N) {
             if (args.push_world) {
                 for (int p = 0; p < args.push_world; ++p)       // 7 xGMI stores + 1 local, 4 bytes each from 16 lanes (64-byte runs)
@@ -828,17 +740,11 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, (MB == 1 ? PBL_MIN_WAVES : 1)) void
     }
 }
 
-#ifdef PBL_PROTO_ROWMAJOR   // experimental build only: the row-major-plane GEMV prototype lives in tools/ (see the file's header)
-#define PBL_PROTO_SECTION_KERNEL
-#include "../../tools/proto_rowmajor_kernel.inc"
-#undef PBL_PROTO_SECTION_KERNEL
-#endif
-
 size_t lds_bytes(uint32_t P, uint32_t max_nch, int mb, int wpb, int split = 1) {
     const size_t xstride = size_t(P) * PBL_PANEL_COLS + 8;
     size_t s = (size_t(mb) * xstride * 2 + 15) & ~size_t(15);
     if (split > 1) s += (size_t(max_nch) + size_t(split) * PBL_WAVE) * mb * sizeof(float2);
-    else s += size_t(wpb) * ((PBL_PROBE & 1) ? (max_nch + 1) / 2 : max_nch) * mb * sizeof(float2);
+    else s += size_t(wpb) * max_nch * mb * sizeof(float2);
     return s + 16;
 }
 
@@ -1179,8 +1085,7 @@ __global__ __launch_bounds__(4 * PBL_WAVE) void pbl_unpack_kernel(pbl_layer L, O
                 constexpr int V = 16 / sizeof(OutT);
                 for (int j = lane * V; j < ncol; j += PBL_WAVE * V) {
                     const u32x4 v = *reinterpret_cast<const u32x4*>(rowbuf + j);
-                    if (PBL_UNPACK_NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst + j));
-                    else *reinterpret_cast<u32x4*>(dst + j) = v;
+                    *reinterpret_cast<u32x4*>(dst + j) = v;
                 }
             } else {
                 for (int j = lane; j < ncol; j += PBL_WAVE) dst[j] = rowbuf[j];
@@ -1253,54 +1158,19 @@ int grouped_groups(const GemvArgs& a, int M, uint32_t max_NRB, uint32_t max_K, u
     return PBL_OK;
 }
 
-template <int WPB, bool SF, int XP = XP_NONE>
-int launch_mb2(int mb, const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-    switch (mb) {
-        case 1: return launch<1, WPB, SF, 1, XP>(a, grid, lds, st);
-        case 2: return launch<2, WPB, SF, 1, XP>(a, grid, lds, st);
-        case 3: return launch<3, WPB, SF, 1, XP>(a, grid, lds, st);
-        case 4: return launch<4, WPB, SF, 1, XP>(a, grid, lds, st);
-        default: return PBL_ERR_INVALID_ARG;
-    }
-}
-template <int WPB, int XP = XP_NONE>
-int launch_mb(int mb, bool sf, const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-    return sf ? launch_mb2<WPB, true, XP>(mb, a, grid, lds, st) : launch_mb2<WPB, false, XP>(mb, a, grid, lds, st);
-}
-// latency mode: S waves per record
-template <int S, int XP = XP_NONE>
-int launch_split(int mb, bool sf, const GemvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-    if (sf) {
-        switch (mb) {
-            case 1: return launch<1, S, true, S, XP>(a, grid, lds, st);
-            case 2: return launch<2, S, true, S, XP>(a, grid, lds, st);
-            case 3: return launch<3, S, true, S, XP>(a, grid, lds, st);
-            case 4: return launch<4, S, true, S, XP>(a, grid, lds, st);
-        }
-    } else {
-        switch (mb) {
-            case 1: return launch<1, S, false, S, XP>(a, grid, lds, st);
-            case 2: return launch<2, S, false, S, XP>(a, grid, lds, st);
-            case 3: return launch<3, S, false, S, XP>(a, grid, lds, st);
-            case 4: return launch<4, S, false, S, XP>(a, grid, lds, st);
-        }
-    }
-    return PBL_ERR_INVALID_ARG;
-}
-#ifndef PBL_SPLIT_TARGET_WAVES
-#define PBL_SPLIT_TARGET_WAVES 8192u
-#endif
-// waves per record so that a launch of `records` records fields about a full chip of waves
-// (256 CUs x 32); more waves per record shorten every wave's serial load -> compute chain
+constexpr uint32_t PBL_SPLIT_TARGET_WAVES = 8192u;   // a full chip of waves (256 CUs x 32)
+constexpr int PBL_THROUGHPUT_WPB = 4;                // waves per workgroup when every wave owns a record
+// waves per record so that a launch of `records` records fields about a full chip of waves;
+// more waves per record shorten every wave's serial load -> compute chain.
+// The third condition holds at s = 1 for every P, so a launch of fewer than PBL_SPLIT_TARGET_WAVES records always splits: the
+// answer 1 means records >= PBL_SPLIT_TARGET_WAVES, which fill the chip at PBL_THROUGHPUT_WPB waves per workgroup.  One wave per
+// workgroup with SPLIT = 1 therefore never ran and is not instantiated.
 int pick_split(uint32_t records, uint32_t P) {
     int s = 1;
     while (s < 8 && records * uint32_t(s) < PBL_SPLIT_TARGET_WAVES && uint32_t(2 * s) <= (P > 1 ? P : 1u) * 2u) s *= 2;
     return s;
 }
 
-#ifndef PBL_GROUPED_WPB
-#define PBL_GROUPED_WPB 4
-#endif
 // THE launch configuration of a group-free GEMV pass (pbl_gemv_route answers from here, so it cannot drift from what is launched).
 // members == 0: one layer of NRB records (route_of: throughput mode, a wave per record and 4 per workgroup, when the records fill
 // the chip; otherwise latency mode, S waves share a record).  members == L >= 1: a fused / grouped launch of L members whose
@@ -1312,30 +1182,38 @@ GemvRoute gemv_route(uint32_t NRB, uint32_t P, int members) {
     GemvRoute g;
     const uint64_t records = uint64_t(NRB) * uint64_t(members > 0 ? members : 1);
     g.split = records >= PBL_SPLIT_TARGET_WAVES ? 1 : pick_split(uint32_t(records), P);
-    g.wpb = g.split > 1 ? g.split : members > 0 ? PBL_GROUPED_WPB : (NRB >= 1024 ? 4 : 1);
+    g.wpb = g.split > 1 ? g.split : PBL_THROUGHPUT_WPB;
     return g;
+}
+
+// THE launcher of pbl_gemv_kernel: one pass of M tokens on route g over `layers` layers (grid.y) of at most `records` records
+// (grid.x) each, P panels and max_nch salient chunks per record at most; sf: PBL_FLAG_SAL_F16 layers may be among them.
+template <int XP = XP_NONE>
+int launch_gemv(GemvRoute g, uint32_t records, int layers, uint32_t P, uint32_t max_nch, int M, bool sf, const GemvArgs& a,
+                hipStream_t st) {
+    if (M < 1 || M > PBL_MAX_TOKENS_PER_LAUNCH) return PBL_ERR_INVALID_ARG;
+    const dim3 grid(g.split > 1 ? records : (records + g.wpb - 1) / g.wpb, layers, 1);
+    const size_t lds = lds_bytes(P, max_nch, M, g.wpb, g.split);
+    using Fn = int (*)(const GemvArgs&, dim3, size_t, hipStream_t);
+#define PBL_MB(MB, W, S) {launch<MB, W, false, S, XP>, launch<MB, W, true, S, XP>}
+#define PBL_CFG(W, S) {PBL_MB(1, W, S), PBL_MB(2, W, S), PBL_MB(3, W, S), PBL_MB(4, W, S)}
+    static constexpr Fn table[4][PBL_MAX_TOKENS_PER_LAUNCH][2] = {PBL_CFG(PBL_THROUGHPUT_WPB, 1), PBL_CFG(2, 2), PBL_CFG(4, 4), PBL_CFG(8, 8)};
+#undef PBL_CFG
+#undef PBL_MB
+    return table[g.split == 8 ? 3 : g.split == 4 ? 2 : g.split == 2 ? 1 : 0][M - 1][sf](a, grid, lds, st);
+}
+
+// one pass of a.M tokens over the single layer a.layer
+template <int XP = XP_NONE>
+int one_pass(GemvRoute g, const GemvArgs& a, void* stream) {
+    const pbl_layer& l = a.layer;
+    return launch_gemv<XP>(g, l.NRB, 1, l.P, l.max_nch, a.M, l.flags & PBL_FLAG_SAL_F16, a, static_cast<hipStream_t>(stream));
 }
 
 // [a, a + na) and [b, b + nb) share a byte
 bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return na && nb && x < y + nb && y < x + na;
-}
-
-// one GEMV pass of a group-free layer with a prologue / epilogue instantiation, on route_of's split / wpb (the caller has checked
-// M against its one-pass limit)
-template <int XP>
-int one_pass(const pbl_layer* layer, int split, int wpb, GemvArgs& a, int M, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool sf = layer->flags & PBL_FLAG_SAL_F16;
-    const dim3 grid(split > 1 ? layer->NRB : (layer->NRB + wpb - 1) / wpb, 1, 1);
-    const size_t lds = lds_bytes(layer->P, layer->max_nch, M, wpb, split);
-    switch (split) {
-        case 8: return launch_split<8, XP>(M, sf, a, grid, lds, st);
-        case 4: return launch_split<4, XP>(M, sf, a, grid, lds, st);
-        case 2: return launch_split<2, XP>(M, sf, a, grid, lds, st);
-        default: return wpb == 4 ? launch_mb<4, XP>(M, sf, a, grid, lds, st) : launch_mb<1, XP>(M, sf, a, grid, lds, st);
-    }
 }
 
 // ---- rotary position embedding of a decode step (pbl_rope_f16) -----------------------------------------------------------------
@@ -1462,24 +1340,22 @@ int pbl_linear_f16(const pbl_layer* layer, const void* x, void* y, int M, int y_
 // least two workgroups per CU; a pass squeezed into a single workgroup per CU (K = 11008 with 3 tokens, 13824x5120 at 20 %
 // salients with 4) is 3-10x slower than the matrix-core kernel, and so is the matrix-core kernel without its K split.
 struct Route {
-    int split, wpb, mb_max;   // GEMV: waves per record, waves per workgroup, tokens per pass
+    GemvRoute g;              // GEMV: waves per record, waves per workgroup
+    int mb_max;               //       tokens per pass
     bool mfma;                // more tokens than one GEMV pass takes and the matrix-core kernel applies
 };
-#ifndef PBL_GEMV_LDS_BUDGET
-#define PBL_GEMV_LDS_BUDGET (80 * 1024)   // two workgroups per CU
-#endif
+constexpr size_t PBL_GEMV_LDS_BUDGET = 80 * 1024;   // two workgroups per CU
 static Route route_of(const pbl_layer* layer, int M, bool x_aligned) {
     Route r;
     if (layer->G != 1) {
-        r.split = 1; r.wpb = 1; r.mb_max = 2;     // the column-group GEMV keeps 2 x 16 accumulators in registers
+        r.g = {1, 1}; r.mb_max = 2;               // the column-group GEMV: a wave per workgroup, 2 x 16 accumulators in registers
         while (r.mb_max > 1 && lds_bytes_groups(layer->P, layer->G, layer->max_nch, r.mb_max, 1) > 96 * 1024) --r.mb_max;
     } else {
         // throughput mode (a wave per record, 4 per workgroup) when there are enough records to fill the
         // chip; otherwise latency mode: S waves share a record
-        const GemvRoute g = gemv_route(layer->NRB, layer->P, 0);
-        r.split = g.split; r.wpb = g.wpb;
+        r.g = gemv_route(layer->NRB, layer->P, 0);
         r.mb_max = PBL_MAX_TOKENS_PER_LAUNCH;
-        while (r.mb_max > 1 && lds_bytes(layer->P, layer->max_nch, r.mb_max, r.wpb, r.split) > PBL_GEMV_LDS_BUDGET) --r.mb_max;
+        while (r.mb_max > 1 && lds_bytes(layer->P, layer->max_nch, r.mb_max, r.g.wpb, r.g.split) > PBL_GEMV_LDS_BUDGET) --r.mb_max;
     }
     // (tiny layers at M <= 8 stay on the GEMV: both are launch-latency bound and the GEMV starts faster)
     r.mfma = M > r.mb_max && (M > 8 || layer->NRB >= 128) && !(layer->K & 7) && x_aligned &&
@@ -1504,7 +1380,7 @@ static Route route_of(const pbl_layer* layer, int M, bool x_aligned) {
     return r;
 }
 
-// what every entry that runs ONE GEMV pass of a group-free layer (one_pass) checks first: PBL_OK and the route, else the entry's
+// what every entry that runs ONE GEMV pass of a group-free layer checks first: PBL_OK and the route, else the entry's
 // return code (a misaligned blob; column groups or more rows than one pass takes: PBL_ERR_UNSUPPORTED)
 static int one_pass_route(const pbl_layer* layer, int M, Route& r) {
     if (reinterpret_cast<uintptr_t>(layer->blob) & 15) return PBL_ERR_MISALIGNED;
@@ -1547,25 +1423,14 @@ int pbl_linear_f16_ws(const pbl_layer* layer, const void* x, void* y, int M, int
         }
     }
     if (layer->G != 1) return linear_groups(layer, x, y, M, y_f32, st);
-    const bool sf = layer->flags & PBL_FLAG_SAL_F16;
-    const int split = r.split, wpb = r.wpb, mb_max = r.mb_max;
-    for (int m0 = 0; m0 < M; m0 += mb_max) {
-        const int mb = M - m0 < mb_max ? M - m0 : mb_max;
+    for (int m0 = 0; m0 < M; m0 += r.mb_max) {
+        const int mb = M - m0 < r.mb_max ? M - m0 : r.mb_max;
         GemvArgs a{};
         a.layer = *layer;
         a.x = static_cast<const _Float16*>(x) + size_t(m0) * layer->K;
         a.y = static_cast<char*>(y) + size_t(m0) * layer->N * esz;
         a.M = mb; a.y_f32 = y_f32; a.grouped = 0;
-        const dim3 grid(split > 1 ? layer->NRB : (layer->NRB + wpb - 1) / wpb, 1, 1);
-        const size_t lds = lds_bytes(layer->P, layer->max_nch, mb, wpb, split);
-        int rc;
-        switch (split) {
-            case 8: rc = launch_split<8>(mb, sf, a, grid, lds, st); break;
-            case 4: rc = launch_split<4>(mb, sf, a, grid, lds, st); break;
-            case 2: rc = launch_split<2>(mb, sf, a, grid, lds, st); break;
-            default: rc = wpb == 4 ? launch_mb<4>(mb, sf, a, grid, lds, st) : launch_mb<1>(mb, sf, a, grid, lds, st);
-        }
-        if (rc != PBL_OK) return rc;
+        if (const int rc = one_pass(r.g, a, stream)) return rc;
     }
     return PBL_OK;
 }
@@ -1585,7 +1450,7 @@ int pbl_linear_bf16(const pbl_layer* layer, const void* x_bf16, void* y, int M, 
     a.x = static_cast<const _Float16*>(x_bf16);                  // (bf16 bits: the XB instantiation reads them as such)
     a.y = y;
     a.M = M; a.y_f32 = y_f32; a.grouped = 0; a.x_bf16 = 1;
-    return one_pass<XP_NONE>(layer, r.split, r.wpb, a, M, stream);
+    return one_pass(r.g, a, stream);
 }
 
 // LLaMA's MLP tail in ONE launch: y [M, N] = down_proj(silu(gate) * up), the GEMV's staging phase building its x row from the fused
@@ -1604,7 +1469,7 @@ int pbl_linear_f16_swiglu(const pbl_layer* layer, const void* gate_up, uint32_t 
     a.y = y;
     a.M = M; a.y_f32 = y_f32; a.grouped = 0;
     a.ldx = ldx; a.up_off = up_off;
-    return one_pass<XP_SWIGLU>(layer, r.split, r.wpb, a, M, stream);
+    return one_pass<XP_SWIGLU>(r.g, a, stream);
 }
 
 // A decoder layer's residual adds in the GEMV's store (XE_RESIDUAL): y [M, N] fp16 = fp16(fp16(layer(x)) + residual), residual
@@ -1623,7 +1488,7 @@ int pbl_linear_f16_residual(const pbl_layer* layer, const void* x, const void* r
     a.y = y;
     a.M = M; a.y_f32 = 0; a.grouped = 0;
     a.residual = static_cast<const _Float16*>(residual); a.ldr = ldr;
-    return one_pass<XP_NONE | XE_RESIDUAL>(layer, r.split, r.wpb, a, M, stream);
+    return one_pass<XP_NONE | XE_RESIDUAL>(r.g, a, stream);
 }
 
 // LLaMA's whole MLP tail in ONE launch: y [M, N] fp16 = fp16(fp16(layer(silu(gate) * up)) + residual) -- pbl_linear_f16_swiglu's
@@ -1646,7 +1511,7 @@ int pbl_linear_f16_swiglu_residual(const pbl_layer* layer, const void* gate_up, 
     a.M = M; a.y_f32 = 0; a.grouped = 0;
     a.ldx = ldx; a.up_off = up_off;
     a.residual = static_cast<const _Float16*>(residual); a.ldr = ldr;
-    return one_pass<XP_SWIGLU | XE_RESIDUAL>(layer, r.split, r.wpb, a, M, stream);
+    return one_pass<XP_SWIGLU | XE_RESIDUAL>(r.g, a, stream);
 }
 
 // HF's apply_rotary_pos_emb for the q and k heads of a fused q/k/v output, in ONE launch (pbl_rope_kernel).  Token m = b * S + s
@@ -1755,8 +1620,6 @@ int pbl_linear_f16_push(const pbl_layer* layer, const void* x, int M, void* cons
     if (layer->G != 1) return PBL_ERR_UNSUPPORTED;
     const Route r = route_of(layer, M, !(reinterpret_cast<uintptr_t>(x) & 15));
     if (M > r.mb_max) return PBL_ERR_UNSUPPORTED;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool sf = layer->flags & PBL_FLAG_SAL_F16;
     GemvArgs a{};
     a.layer = *layer;
     a.layer.bias = rank == 0 ? layer->bias : nullptr;         // (the bias is added once: by rank 0's partial)
@@ -1768,15 +1631,7 @@ int pbl_linear_f16_push(const pbl_layer* layer, const void* x, int M, void* cons
         if (!peer_bufs[p]) return PBL_ERR_INVALID_ARG;
         a.push_peer[p] = static_cast<uint8_t*>(peer_bufs[p]);
     }
-    const int split = r.split, wpb = r.wpb;
-    const dim3 grid(split > 1 ? layer->NRB : (layer->NRB + wpb - 1) / wpb, 1, 1);
-    const size_t lds = lds_bytes(layer->P, layer->max_nch, M, wpb, split);
-    switch (split) {
-        case 8: return launch_split<8>(M, sf, a, grid, lds, st);
-        case 4: return launch_split<4>(M, sf, a, grid, lds, st);
-        case 2: return launch_split<2>(M, sf, a, grid, lds, st);
-        default: return wpb == 4 ? launch_mb<4>(M, sf, a, grid, lds, st) : launch_mb<1>(M, sf, a, grid, lds, st);
-    }
+    return one_pass(r.g, a, stream);
 }
 
 // The largest M pbl_linear_f16_push takes for this shard: route_of's one-pass limit, which follows the shard's fullest record
@@ -1813,27 +1668,23 @@ int pbl_gemv_f16_grouped(const pbl_layer* layers_dev, const void* const* x_dev, 
     a.layers = layers_dev; a.xs = x_dev; a.ys = y_dev; a.M = M; a.y_f32 = y_f32; a.grouped = 1; a.Lc = Lc;
     if (any_groups & 1) return grouped_groups(a, M, max_NRB, max_K, max_nch, static_cast<hipStream_t>(stream));
     const uint32_t P = (max_K + PBL_PANEL_COLS - 1) / PBL_PANEL_COLS;
-    const bool sf = (any_groups & 2) != 0;   // bit 1: the group may contain PBL_FLAG_SAL_F16 layers
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // few records in total (fused q/k/v, gate+up at decode time): latency mode, S waves per record
-    const GemvRoute g = gemv_route(max_NRB, P, Lc);
-    const int split = g.split;
-    if (split > 1) {
-        const dim3 grid(max_NRB, Lc, 1);
-        const size_t lds = lds_bytes(P, max_nch, M, split, split);
-        switch (split) {
-            case 8: return launch_split<8>(M, sf, a, grid, lds, st);
-            case 4: return launch_split<4>(M, sf, a, grid, lds, st);
-            default: return launch_split<2>(M, sf, a, grid, lds, st);
-        }
-    }
-    const int wpb = g.wpb;                    // (PBL_GROUPED_WPB: the instantiation below)
-    const dim3 grid((max_NRB + wpb - 1) / wpb, Lc, 1);
-    return launch_mb<PBL_GROUPED_WPB>(M, sf, a, grid, lds_bytes(P, max_nch, M, wpb), st);
+    // bit 1 of any_groups: the group may contain PBL_FLAG_SAL_F16 layers
+    return launch_gemv(gemv_route(max_NRB, P, Lc), max_NRB, Lc, P, max_nch, M, (any_groups & 2) != 0, a, static_cast<hipStream_t>(stream));
 }
 
-static int fused_launch(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream);
-static int fused_launch_norm(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream);
+// A fused launch of Lc members reading K columns each (column groups: the column-group kernel).  With a.norm_w set (group-free
+// members only: the caller has checked) the RMSNorm prologue stages x, and what one pass under route_of's LDS budget cannot take
+// is declined.
+static int fused_launch(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (group_flags & 1) { a.Lc = Lc; return grouped_groups(a, M, max_NRB, K, max_nch, st); }
+    const uint32_t P = (K + PBL_PANEL_COLS - 1) / PBL_PANEL_COLS;
+    const bool sf = (group_flags & 2) != 0;
+    const GemvRoute g = gemv_route(max_NRB, P, Lc);
+    if (!a.norm_w) return launch_gemv(g, max_NRB, Lc, P, max_nch, M, sf, a, st);
+    if (lds_bytes(P, max_nch, M, g.wpb, g.split) > PBL_GEMV_LDS_BUDGET) return PBL_ERR_UNSUPPORTED;
+    return launch_gemv<XP_RMSNORM>(g, max_NRB, Lc, P, max_nch, M, sf, a, st);
+}
 
 int pbl_gemv_f16_fused(const pbl_layer* layers_dev, const uint64_t* y_off_dev, const void* x, void* y, int Lc, int M,
                        uint32_t ldy, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, int y_f32, void* stream) {
@@ -1891,56 +1742,8 @@ static int fused_host(const pbl_layer* layers_host, const uint64_t* y_off_host, 
     a.x_shared = static_cast<const _Float16*>(x); a.y_shared = y; a.ldy = ldy;
     if (norm_w) {
         a.norm_w = static_cast<const _Float16*>(norm_w); a.norm_eps = norm_eps;
-        return fused_launch_norm(a, Lc, M, max_NRB, K, max_nch, group_flags, stream);
     }
     return fused_launch(a, Lc, M, max_NRB, K, max_nch, group_flags, stream);
 }
-
-// fused_launch's group-free route with the RMSNorm prologue, declining what one pass under route_of's LDS budget cannot take
-static int fused_launch_norm(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream) {
-    const uint32_t P = (K + PBL_PANEL_COLS - 1) / PBL_PANEL_COLS;
-    const bool sf = (group_flags & 2) != 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const GemvRoute g = gemv_route(max_NRB, P, Lc);
-    const int split = g.split, wpb = g.wpb;   // (split == 1: PBL_GROUPED_WPB, the instantiation below)
-    const size_t lds = split > 1 ? lds_bytes(P, max_nch, M, split, split) : lds_bytes(P, max_nch, M, wpb);
-    if (lds > PBL_GEMV_LDS_BUDGET) return PBL_ERR_UNSUPPORTED;
-    const dim3 grid(split > 1 ? max_NRB : (max_NRB + wpb - 1) / wpb, Lc, 1);
-    switch (split) {
-        case 8: return launch_split<8, XP_RMSNORM>(M, sf, a, grid, lds, st);
-        case 4: return launch_split<4, XP_RMSNORM>(M, sf, a, grid, lds, st);
-        case 2: return launch_split<2, XP_RMSNORM>(M, sf, a, grid, lds, st);
-        default: return launch_mb<PBL_GROUPED_WPB, XP_RMSNORM>(M, sf, a, grid, lds, st);
-    }
-}
-
-static int fused_launch(GemvArgs& a, int Lc, int M, uint32_t max_NRB, uint32_t K, uint32_t max_nch, int group_flags, void* stream) {
-    const int y_f32 = a.y_f32;
-    (void)y_f32;
-    if (group_flags & 1) { a.Lc = Lc; return grouped_groups(a, M, max_NRB, K, max_nch, static_cast<hipStream_t>(stream)); }
-    const uint32_t P = (K + PBL_PANEL_COLS - 1) / PBL_PANEL_COLS;
-    const bool sf = (group_flags & 2) != 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const GemvRoute g = gemv_route(max_NRB, P, Lc);
-    const int split = g.split;
-    if (split > 1) {
-        const dim3 grid(max_NRB, Lc, 1);
-        const size_t lds = lds_bytes(P, max_nch, M, split, split);
-        switch (split) {
-            case 8: return launch_split<8>(M, sf, a, grid, lds, st);
-            case 4: return launch_split<4>(M, sf, a, grid, lds, st);
-            default: return launch_split<2>(M, sf, a, grid, lds, st);
-        }
-    }
-    const int wpb = g.wpb;                    // (PBL_GROUPED_WPB: the instantiation below)
-    const dim3 grid((max_NRB + wpb - 1) / wpb, Lc, 1);
-    return launch_mb<PBL_GROUPED_WPB>(M, sf, a, grid, lds_bytes(P, max_nch, M, wpb), st);
-}
-
-#ifdef PBL_PROTO_ROWMAJOR
-#define PBL_PROTO_SECTION_HOST
-#include "../../tools/proto_rowmajor_kernel.inc"
-#undef PBL_PROTO_SECTION_HOST
-#endif
 
 }  // extern "C"

@@ -8,7 +8,7 @@ threshold fails that test instead of silently thinning the GPU grid.
   via "P"        the split is capped by the panel count (2 at P = 1, 4 at P = 2 or 3, 8 from P = 4): few records
   via "records"  the split is set by the record count (4 from 2048 records, 2 from 4096, 1 from 8192) at a P that would allow more
 
-SPLIT = 1 with WPB = 1 is unreachable with the default PBL_SPLIT_TARGET_WAVES (fewer than 8192 records always split): no row.
+SPLIT = 1 with WPB = 1 does not exist (fewer than 8192 records always split, more run 4 waves per workgroup): no row.
 
 `rich` rows carry a bias, exception entries (one of them in the last record) and an N that is not a multiple of 16; there is one
 per SPLIT value and family.  The layers are built directly on the format's grid (random signs on per-row hi / lo, random 8-bit

@@ -1,7 +1,7 @@
 """-m "not gpu": which pbl_gemv_kernel configuration a launch gets (pbl_gemv_route, the helper route_of / fused_launch /
-fused_launch_norm / pbl_gemv_f16_grouped ask) and whether the case table of test_gpu_gemv_configs.py (gemv_cfg_cases.py) reaches
+pbl_gemv_f16_grouped ask) and whether the case table of test_gpu_gemv_configs.py (gemv_cfg_cases.py) reaches
 every configuration in both families.  The library answers; nothing here restates pick_split.
-SPLIT = 1 with WPB = 1 is unreachable with the default PBL_SPLIT_TARGET_WAVES: asserted over a sweep below, no case contrived."""
+SPLIT = 1 with WPB = 1 no longer exists (it could never be launched): asserted over a sweep below, no case contrived."""
 import ctypes as C
 import functools
 
@@ -50,8 +50,8 @@ def test_the_table_reaches_every_configuration_through_both_limits(family):
 
 
 def test_split_1_with_one_wave_per_workgroup_is_unreachable():
-    """fewer than PBL_SPLIT_TARGET_WAVES records always share a record between at least 2 waves, and from there on a single layer
-    has >= 1024 records (WPB = 4); fused launches use WPB = 4 throughout"""
+    """the configuration no longer exists: it is not instantiated, and no route names it.  Fewer than PBL_SPLIT_TARGET_WAVES (8192)
+    records always share a record between at least 2 waves, and from there on every launch runs 4 waves per workgroup"""
     seen = set()
     nrbs = sorted(set(list(range(1, 70)) + [2 ** k + d for k in range(6, 21) for d in (-1, 0, 1)] + [1 << 24 >> 4]))
     for members in (0, 1, 2, 3, 4, 7, 64):

@@ -139,6 +139,30 @@ def test_the_library_builds_without_warnings():
     assert callable(g.build)
 
 
+def test_an_edited_private_header_makes_the_library_stale(tmp_path):
+    """build()'s stamp digests every header the sources include, csrc/pbl_p2p_layout.h among them: one changed byte there and a
+    library with a matching stamp is stale.  A copy of the sources and a fake library and stamp: nothing is compiled."""
+    import shutil
+    import __graft_entry__ as g
+    shutil.copytree(os.path.join(REPO, "pb_llm_amd", "csrc"), tmp_path / "pb_llm_amd" / "csrc")
+    shutil.copytree(os.path.join(REPO, "include"), tmp_path / "include")
+    srcs, deps = g._lib_sources(str(tmp_path))
+    assert all(os.path.exists(s) for s in deps) and set(srcs) < set(deps)
+    included = set()
+    for s in deps:                                                      # every quoted include of every file is in the digest
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(s).read(), re.M):
+            included.add(os.path.normpath(os.path.join(os.path.dirname(s), inc)))
+    assert included and included <= set(deps), included - set(deps)
+    lib = str(tmp_path / "libpbl.so")
+    open(lib, "wb").close()
+    g._stamp(lib, deps)
+    assert not g._stale(lib, deps)
+    header = tmp_path / "pb_llm_amd" / "csrc" / "pbl_p2p_layout.h"
+    assert str(header) in deps
+    header.write_bytes(header.read_bytes() + b"\n")
+    assert g._stale(lib, deps)
+
+
 def test_activation_entry_points_check_their_arguments():
     L = _lib.lib()
     lay = _lib.PblLayer(None, None, 64, 1024, 2, 1, 4, 0xE, 8, 0)
