@@ -435,18 +435,20 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs ar
     // Two tile registers, rotated in phase 1 (t0 <- t1 <- the panel two steps on), and this wave's first salient round.  The
     // weight stream is read once: every load of it is non-temporal.
     u32x4 t0 = {0, 0, 0, 0}, t1 = {0, 0, 0, 0};
+    // One salient round's loads: chunk min(c, nch - 1) of the three streams.  The bases are wave-uniform and the chunk index is
+    // unsigned, so each load takes an SGPR base and ONE 32-bit lane offset (no 64-bit address arithmetic per round).
+    auto sal_fetch = [&](int c, uint32_t& c0, u32x4& d4, u32x4& q4) {
+        const uint32_t cn = uint32_t(c < nch ? c : nch - 1);
+        c0 = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(col0p) + size_t(cn * 2u));
+        d4 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(deltap) + size_t(cn * 16u)));
+        q4 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(codep) + size_t(cn * 16u)));
+    };
     uint32_t s_c0 = 0;
     u32x4 s_d4 = {0, 0, 0, 0}, s_q4 = {0, 0, 0, 0};
     if (active) {
         if (wslot < P) t0 = __builtin_nontemporal_load(tiles + wslot * 64);
         if (wslot + WSTEP < P) t1 = __builtin_nontemporal_load(tiles + (wslot + WSTEP) * 64);
-        if (nch > wslot * PBL_WAVE) {
-            const int c_first = wslot * PBL_WAVE + lane;
-            const int cc = c_first < nch ? c_first : nch - 1;
-            s_c0 = col0p[cc];
-            s_d4 = __builtin_nontemporal_load(deltap + cc);
-            s_q4 = __builtin_nontemporal_load(codep + cc);
-        }
+        if (nch > wslot * PBL_WAVE) sal_fetch(wslot * PBL_WAVE + lane, s_c0, s_d4, s_q4);
     }
 
     // ---- phase 0: stage x ---------------------------------------------------------
@@ -592,6 +594,14 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs ar
         t1 = tn;
     }
 
+    // row-owner lanes: lane l owns row rho(l) (4 lanes per row).  Their row parameters are requested here, in front of the
+    // reduction: phase 3 must not wait on HBM, and the first salient round -- which waits for its own loads in issue order --
+    // finds these already landed instead of exposing their latency.
+    const int rho = ((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1);
+    const int sub = lane & 3;
+    const pbl_rowparams pr = reinterpret_cast<const pbl_rowparams*>(rec + PBL_REC_PARAMS_OFF)[rho];
+    const pbl_rowinfo ri = reinterpret_cast<const pbl_rowinfo*>(rec + PBL_REC_ROWINFO_OFF)[rho];
+
     // reduce the 16 row accumulators now: from here on one register per token carries the
     // binary result (lane l holds row rho(l), see transpose_reduce16)
     float accsum[MB], X[MB];
@@ -601,11 +611,6 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs ar
         accsum[m] = transpose_reduce16(acc[m], lane);
     }
 
-    // row-owner lanes: lane l owns row rho(l) (4 lanes per row)
-    const int rho = ((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1);
-    const int sub = lane & 3;
-    const pbl_rowparams pr = reinterpret_cast<const pbl_rowparams*>(rec + PBL_REC_PARAMS_OFF)[rho];
-    const pbl_rowinfo ri = reinterpret_cast<const pbl_rowinfo*>(rec + PBL_REC_ROWINFO_OFF)[rho];   // issued early: phase 3 must not wait on HBM
     // SF layers in a mixed grouped launch are told apart at run time (wave-uniform)
     const bool sf = SF && (L.flags & PBL_FLAG_SAL_F16);
     const uint8_t* crow = sal + PBL_SAL_CROW_OFF(nchu, uint32_t(ntail));
@@ -617,44 +622,58 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs ar
         const uint32_t xbase = uint32_t(reinterpret_cast<uintptr_t>(xs));      // LDS byte offset of x
         const uint32_t tok_stride = uint32_t(xstride) * 2u;
         const uint32_t zaddr = xbase + 2u * uint32_t(Kp);                      // a zero slot
-        for (int base = wslot * PBL_WAVE; base < nch; base += WSTEP * PBL_WAVE) {
-            const int c = base + lane;
-            const bool valid = c < nch;
-            const int cc = valid ? c : nch - 1;
-            const uint32_t c0 = s_c0;
-            const u32x4 d4 = s_d4, q4 = s_q4;
-            if (base + WSTEP * PBL_WAVE < nch) {
-                const int cn = c + WSTEP * PBL_WAVE < nch ? c + WSTEP * PBL_WAVE : nch - 1;
-                s_c0 = col0p[cn];
-                s_d4 = __builtin_nontemporal_load(deltap + cn);
-                s_q4 = __builtin_nontemporal_load(codep + cn);
-            }
-            float Q[MB], S[MB];
+        constexpr int RSTEP = WSTEP * PBL_WAVE;
+        // Two rounds per trip over two register sets (the inner loop is unrolled, so h is a constant): round h computes from set
+        // h while the next round's loads land in the other set -- set 0 is (s_c0, s_d4, s_q4), loaded before phase 0 and by
+        // every odd round; set 1 lives inside one trip.  No register is copied between rounds.  (The round is written out in place: inside a lambda hipcc no longer proves
+        // the blob's pointers global, and every load of the kernel becomes a flat load.)
+        for (int base0 = wslot * PBL_WAVE; base0 < nch; base0 += 2 * RSTEP) {
+            uint32_t rc0[2];
+            u32x4 rd4[2], rq4[2];
+            rc0[0] = s_c0; rd4[0] = s_d4; rq4[0] = s_q4;
 #pragma unroll
-            for (int m = 0; m < MB; ++m) { Q[m] = 0.f; S[m] = 0.f; }
-            int cnt = 16;
-            if (base + PBL_WAVE > nfull) {
-                if (cc >= nfull) cnt = tailcnt[cc - nfull];
-                if (!valid) cnt = 0;
-            }
-            if (SF && sf) {
-                // this chunk's row -> its (scale, zero) from the row-owner lane (no memory round trip)
-                const int crw = crow[cc];
-                const int owner = ((crw & 8) << 2) | ((crw & 4) << 2) | ((crw & 2) << 2) | ((crw & 1) << 2);
-                const float ss = __shfl(pr.sscale, owner, PBL_WAVE), sz = __shfl(pr.szero, owner, PBL_WAVE);
-                if (base + PBL_WAVE <= nfull)
-                    chunk_accumulate<MB, false, true>(xbase, tok_stride, c0, d4, q4, 16, zaddr, c_one, ss, sz, Q, S);
-                else
-                    chunk_accumulate<MB, true, true>(xbase, tok_stride, c0, d4, q4, cnt, zaddr, c_one, ss, sz, Q, S);
-            } else if (base + PBL_WAVE <= nfull) {
-                chunk_accumulate<MB, false, false>(xbase, tok_stride, c0, d4, q4, 16, zaddr, c_one, 0.f, 0.f, Q, S);
-            } else {
-                chunk_accumulate<MB, true, false>(xbase, tok_stride, c0, d4, q4, cnt, zaddr, c_one, 0.f, 0.f, Q, S);
-            }
-            if (valid) {
+            for (int h = 0; h < 2; ++h) {
+                const int base = base0 + h * RSTEP;
+                if (h && base >= nch) break;
+                // every round first waits for its own set, explicitly, and only then requests the next one.  Left to hipcc, the wait
+                // lands at the set's first use BEHIND the new requests -- vmcnt counts in issue order, so it would wait for those
+                // too and the prefetch would hide nothing (measured: a 4-token launch, one wave per SIMD, 12 % slower).
+                __builtin_amdgcn_s_waitcnt(0x0F70);                     // s_waitcnt vmcnt(0) alone
+                if (base + RSTEP < nch) {
+                    if (h) sal_fetch(base + RSTEP + lane, s_c0, s_d4, s_q4);
+                    else sal_fetch(base + RSTEP + lane, rc0[1], rd4[1], rq4[1]);
+                }
+                const int c = base + lane;
+                const bool full = base + PBL_WAVE <= nfull;             // wave-uniform: 64 full chunks, every lane valid
+                const bool valid = full || c < nch;
+                const int cc = valid ? c : nch - 1;
+                float Q[MB], S[MB];
 #pragma unroll
-                for (int m = 0; m < MB; ++m)   // code mode: undo the 1024 code bias here, once per chunk
-                    part[size_t(m) * L.max_nch + c] = make_float2((SF && sf) ? Q[m] : fmaf(-1024.f, S[m], Q[m]), S[m]);
+                for (int m = 0; m < MB; ++m) { Q[m] = 0.f; S[m] = 0.f; }
+                int cnt = 16;
+                if (!full) {
+                    if (cc >= nfull) cnt = tailcnt[cc - nfull];
+                    if (!valid) cnt = 0;
+                }
+                if (SF && sf) {
+                    // this chunk's row -> its (scale, zero) from the row-owner lane (no memory round trip)
+                    const int crw = crow[cc];
+                    const int owner = ((crw & 8) << 2) | ((crw & 4) << 2) | ((crw & 2) << 2) | ((crw & 1) << 2);
+                    const float ss = __shfl(pr.sscale, owner, PBL_WAVE), sz = __shfl(pr.szero, owner, PBL_WAVE);
+                    if (full)
+                        chunk_accumulate<MB, false, true>(xbase, tok_stride, rc0[h], rd4[h], rq4[h], 16, zaddr, c_one, ss, sz, Q, S);
+                    else
+                        chunk_accumulate<MB, true, true>(xbase, tok_stride, rc0[h], rd4[h], rq4[h], cnt, zaddr, c_one, ss, sz, Q, S);
+                } else if (full) {
+                    chunk_accumulate<MB, false, false>(xbase, tok_stride, rc0[h], rd4[h], rq4[h], 16, zaddr, c_one, 0.f, 0.f, Q, S);
+                } else {
+                    chunk_accumulate<MB, true, false>(xbase, tok_stride, rc0[h], rd4[h], rq4[h], cnt, zaddr, c_one, 0.f, 0.f, Q, S);
+                }
+                if (valid) {
+#pragma unroll
+                    for (int m = 0; m < MB; ++m)   // code mode: undo the 1024 code bias here, once per chunk
+                        part[size_t(m) * L.max_nch + c] = make_float2((SF && sf) ? Q[m] : fmaf(-1024.f, S[m], Q[m]), S[m]);
+                }
             }
         }
     }
