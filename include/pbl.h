@@ -566,6 +566,35 @@ int pbl_prefill_attn_f16(const void* q, const int64_t* q_stride, const void* k_n
                          const int64_t* v_stride, void* k_cache, void* v_cache, int B, int S, int Hq, int Hkv, int D, int max_len,
                          float scaling, int64_t* pos, void* out, uint32_t ldo, void* stream);
 
+/* The FP8 KV cache (csrc/pbl_kv8.hip; harness.DecodeSession(..., kv_cache="fp8") / harness.generate(..., kv_cache="fp8")): the three
+ * entries above over a cache that takes half the bytes.
+ *   The format.  A cache row -- one token of one kv head, D = 64 or 128 values -- is D bytes of OCP e4m3fn and ONE power-of-two scale:
+ *   k_cache / v_cache [B, Hkv, max_len, D] uint8, contiguous, 16-B aligned; k_scale / v_scale [B, Hkv, max_len] fp32.  For a row x of
+ *   fp16 values (the rotated k, the raw v: what the fp16 entries store): amax = max |x|; e = the smallest integer with amax <= 448 2^e,
+ *   clamped to [-15, 7] (an all-zero row: -15); scale = 2^e; byte j = e4m3fn(x_j / 2^e), round to nearest even.  After the clamp at
+ *   e = 7 a row with amax > 57344 (+-inf included) saturates at +-448; a NaN element becomes a NaN byte (0x7f / 0xff) and does not
+ *   enter amax.  With e in [-15, 7] every dequantised value byte * 2^e is an fp16 value, and a power-of-two scale commutes with every
+ *   rounding of the attention kernels: each entry below returns BIT FOR BIT what its fp16 counterpart returns over a cache that
+ *   holds the dequantised rows.
+ *   pbl_rope_append_kv8   pbl_rope_append_f16: the same q_out; the rotated k heads and the raw v heads quantised into cache rows
+ *                         [pos, pos + S) and their scales into the same rows of k_scale / v_scale.
+ *   pbl_decode_attn_kv8   pbl_decode_attn_f16: the same kernels, key-to-lane mapping, split rule, reduction orders, workspace
+ *                         (pbl_decode_attn_workspace_bytes) and combine; rows beyond pos + S are never read, scales included.
+ *   pbl_prefill_attn_kv8  pbl_prefill_attn_f16: k_new / v_new quantised into cache rows [p, p + S), then the same attention kernel
+ *                         over keys and values read back -- dequantised -- from the cache, then *pos += S.
+ * Each has the checks, the scope and the error codes of its fp16 counterpart; the scale arrays are outputs of the appends and inputs
+ * of the attention for the overlap checks (NULL: PBL_ERR_INVALID_ARG; not 4-B aligned: PBL_ERR_MISALIGNED). */
+int pbl_rope_append_kv8(const void* qkv, uint32_t ld, uint32_t q_off, uint32_t k_off, uint32_t v_off, int B, int S, int Hq, int Hkv,
+                        int D, const void* cos, const void* sin, int cos_dim, int64_t cos_sb, int64_t cos_ss, void* q_out,
+                        const int64_t* q_ostride, void* k_cache, void* v_cache, void* k_scale, void* v_scale, int max_len,
+                        const int64_t* pos, void* stream);
+int pbl_decode_attn_kv8(const void* q, const int64_t* q_stride, const void* k_cache, const void* v_cache, const void* k_scale,
+                        const void* v_scale, int B, int S, int Hq, int Hkv, int D, int max_len, float scaling, int64_t* pos, void* out,
+                        uint32_t ldo, void* ws, size_t ws_bytes, void* stream);
+int pbl_prefill_attn_kv8(const void* q, const int64_t* q_stride, const void* k_new, const int64_t* k_stride, const void* v_new,
+                         const int64_t* v_stride, void* k_cache, void* v_cache, void* k_scale, void* v_scale, int B, int S, int Hq,
+                         int Hkv, int D, int max_len, float scaling, int64_t* pos, void* out, uint32_t ldo, void* stream);
+
 /* Token selection of a decode step (csrc/pbl_select.hip; harness.DecodeSession / harness.generate): temperature, top-k, top-p, the
  * draw and the eos / pad bookkeeping of a generation loop in one launch per step (B > 1: a second, one-wave launch that counts the
  * unfinished rows and advances the step).

@@ -63,7 +63,8 @@ EXPORTS = ["pbl_status_string", "pbl_version", "pbl_pack_dense_f32", "pbl_pack_d
            "pbl_gemm_f16_image_ws", "pbl_gemv_f16_fused_norm_host", "pbl_linear_f16_swiglu",
            "pbl_linear_f16_residual", "pbl_linear_f16_swiglu_residual", "pbl_rope_f16",
            "pbl_rope_append_f16", "pbl_decode_attn_workspace_bytes", "pbl_decode_attn_f16", "pbl_prefill_attn_f16", "pbl_select_token_f16",
-           "pbl_score_tokens_f16", "pbl_gemv_route", "pbl_spec_verify_f16", "pbl_ngram_draft"]
+           "pbl_score_tokens_f16", "pbl_gemv_route", "pbl_spec_verify_f16", "pbl_ngram_draft",
+           "pbl_rope_append_kv8", "pbl_decode_attn_kv8", "pbl_prefill_attn_kv8"]
 
 
 def lib() -> C.CDLL:
@@ -243,6 +244,15 @@ def lib() -> C.CDLL:
     L.pbl_prefill_attn_f16.restype = C.c_int
     L.pbl_prefill_attn_f16.argtypes = [vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, vp, C.c_int,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, u32, vp]
+    L.pbl_rope_append_kv8.restype = C.c_int
+    L.pbl_rope_append_kv8.argtypes = [vp, u32, u32, u32, u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64,
+                                      C.c_int64, vp, C.POINTER(C.c_int64), vp, vp, vp, vp, C.c_int, vp, vp]
+    L.pbl_decode_attn_kv8.restype = C.c_int
+    L.pbl_decode_attn_kv8.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_float, vp, vp, u32, vp, sz, vp]
+    L.pbl_prefill_attn_kv8.restype = C.c_int
+    L.pbl_prefill_attn_kv8.argtypes = [vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, vp, vp, vp,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, u32, vp]
     L.pbl_select_token_f16.restype = C.c_int
     L.pbl_select_token_f16.argtypes = [vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp, C.c_int64, vp, vp, C.c_int,
                                        C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]

@@ -24,6 +24,7 @@
 
 #include "../../include/pbl.h"
 #include "pbl_p2p_layout.h"
+#include "pbl_rope_math.h"
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -1236,31 +1237,7 @@ bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
 }
 
 // ---- rotary position embedding of a decode step (pbl_rope_f16) -----------------------------------------------------------------
-struct RopeArgs {
-    const uint16_t* qkv;            // [M, ld] fp16: q heads at column q_off, k heads at k_off (token m = b * S + s)
-    const uint16_t* cos;            // cos / sin [.., D] fp16: the row of token (b, s) at b * c_sb + s * c_ss (0: broadcast)
-    const uint16_t* sin;
-    uint16_t* q_out;                // element (b, h, s, d) at b * ob + h * oh + s * os + d
-    uint16_t* k_out;
-    int64_t c_sb, c_ss;
-    int64_t q_ob, q_oh, q_os, k_ob, k_oh, k_os;
-    uint32_t ld, q_off, k_off;
-    int S, Hq, H, half, pairs;      // H = Hq + Hkv; pairs = M * H * half
-};
-
-// a value the compiler cannot trace back to an fp16 operand: the arithmetic on it stays fp32 (no fp16 / mixed-precision rewrite)
-__device__ __forceinline__ float opaque(float v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-// (a * b) rounded to fp16, as torch's `*` on half tensors: an fp32 product (exact for two fp16 values), one rounding.  The product
-// is materialised before the rounding: fptrunc(fmul) would otherwise become v_fma_mixlo_f16 with a +0 addend, which turns a -0
-// product into +0.
-__device__ __forceinline__ float mul_f16(float a, float b) {
-#pragma clang fp contract(off)
-    return opaque(float(_Float16(opaque(opaque(a) * opaque(b)))));
-}
-
+// (RopeArgs and the fp16 products mul_f16: pbl_rope_math.h)
 // HF's apply_rotary_pos_emb on half tensors, one (d, d + D/2) pair per thread: q * cos and rotate_half(q) * sin each rounded to
 // fp16, then their sum rounded to fp16 -- the three torch kernels' roundings, never contracted into an fma.  inf / NaN propagate.
 __global__ __launch_bounds__(256) void pbl_rope_kernel(RopeArgs a) {

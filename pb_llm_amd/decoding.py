@@ -18,6 +18,8 @@ DECODE_ATTENTION = True
 # (tools/bench_prefill_attention.py compares the two).  Read HERE when a forward runs.
 PREFILL_ATTENTION = False
 _DECODE_CACHE = None                    # the DecodeCache class, made on first use (transformers is imported lazily)
+_KV8_LAYER = None                       # the FP8 cache's layer class, likewise
+KV_CACHE_FORMATS = ("fp16", "fp8")      # DecodeSession(..., kv_cache=) / generate(..., kv_cache=)
 
 
 def _decode_cache_layer(cache, layer_idx: int, batch: int, n_kv: int, head_dim: int):
@@ -53,10 +55,86 @@ def _prefill_cache_layer(cache, layer_idx: int, batch: int, seq: int, n_q: int, 
     return lay
 
 
+def _kv8_cache_layer(cache, layer_idx: int):
+    """the FP8 layer of `cache` for decoder layer layer_idx (DecodeCache(..., kv_cache="fp8")) -- else None.  A folded layer that finds
+    one appends and attends with the FP8 entries (runtime.rope_append_kv8 / decode_attention_kv8 / prefill_attention_kv8) whatever
+    DECODE_ATTENTION and PREFILL_ATTENTION say: HF's attention cannot read this cache, so there is no other path."""
+    if _KV8_LAYER is None or _DECODE_CACHE is None or not isinstance(cache, _DECODE_CACHE) or layer_idx is None \
+            or layer_idx >= len(cache.layers):
+        return None
+    lay = cache.layers[layer_idx]
+    return lay if type(lay) is _KV8_LAYER and lay.is_initialized else None
+
+
+def _kv8_layer_class():
+    global _KV8_LAYER
+    if _KV8_LAYER is None:
+        from transformers.cache_utils import StaticLayer
+
+        class Kv8StaticLayer(StaticLayer):
+            """A StaticLayer whose rows are FP8 (the format: runtime.kv8_quantize): keys / values uint8 [B, Hkv, max_len, D] with one
+            fp32 power-of-two scale per row in key_scales / value_scales [B, Hkv, max_len].  cumulative_length, get_seq_length, the
+            mask helpers and reset work as in StaticLayer; update() raises, because HF's attention cannot read these rows -- only
+            folded layers (fuse_decode_(epilogues=True)) append to and attend over it.  runtime.kv8_dequantize(lay.keys,
+            lay.key_scales) shows what it holds."""
+
+            def lazy_initialization(self, key_states: torch.Tensor, value_states: torch.Tensor) -> None:
+                self.dtype, self.device = torch.uint8, key_states.device
+                self.batch_size, self.num_heads = key_states.shape[:2]
+                self.k_head_dim = self.v_head_dim = key_states.shape[-1]
+                rows = (self.batch_size, self.num_heads, self.max_cache_len)
+                self.keys = torch.zeros(*rows, self.k_head_dim, dtype=torch.uint8, device=self.device)
+                self.values = torch.zeros(*rows, self.v_head_dim, dtype=torch.uint8, device=self.device)
+                self.key_scales = torch.zeros(rows, dtype=torch.float32, device=self.device)
+                self.value_scales = torch.zeros(rows, dtype=torch.float32, device=self.device)
+                self.cumulative_length = self.cumulative_length.to(self.device)
+                self.is_initialized = True
+
+            def update(self, key_states, value_states, *args, **kwargs):
+                raise RuntimeError("the FP8 KV cache is written by the HIP entries of folded layers (fuse_decode_(epilogues=True)) only: "
+                                   "StaticLayer.update / HF's attention cannot use it")
+
+            def reset(self) -> None:
+                super().reset()
+                if self.is_initialized:
+                    self.key_scales.zero_()
+                    self.value_scales.zero_()
+
+        Kv8StaticLayer.__qualname__ = "Kv8StaticLayer"
+        _KV8_LAYER = Kv8StaticLayer
+    return _KV8_LAYER
+
+
+def _kv8_refusal(model: nn.Module, batch: int, max_length: int) -> str | None:
+    """why DecodeSession(model, batch, max_length, kv_cache="fp8") cannot run -- the first condition that fails -- or None"""
+    from . import fusion
+    try:
+        from transformers.models.llama.modeling_llama import LlamaDecoderLayer
+    except ImportError:
+        return "transformers' LLaMA model is not importable"
+    layers = [m for m in model.modules() if isinstance(m, LlamaDecoderLayer)]
+    cfg = model.config.get_text_config(decoder=True)
+    if not layers or len(layers) != cfg.num_hidden_layers \
+            or not all(getattr(lay.forward, "__func__", None) is fusion._folded_layer_forward for lay in layers):
+        return "every decoder layer must be a folded layer of fuse_decode_(model, epilogues=True): no other layer can read this cache"
+    if model.get_input_embeddings().weight.dtype != torch.float16:
+        return "the model must be fp16"
+    head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+    if head_dim not in (64, 128):
+        return f"head_dim must be 64 or 128, not {head_dim}"
+    if batch > 4:
+        return f"batch must be at most 4, not {batch}"
+    if max_length > 65536:
+        return f"max_length must be at most 65536, not {max_length}"
+    if not runtime.kv8_ok(batch, 1, cfg.num_attention_heads, cfg.num_key_value_heads, head_dim, max_length):
+        return "runtime.kv8_ok declines these heads"
+    return None
+
+
 def _decode_cache_class():
     global _DECODE_CACHE
     if _DECODE_CACHE is None:
-        from transformers.cache_utils import StaticCache
+        from transformers.cache_utils import StaticCache, StaticLayer
 
         class DecodeCache(StaticCache):
             """transformers' StaticCache for an UNPADDED batch whose rows all share one position, allocated up front (so that a
@@ -65,10 +143,18 @@ def _decode_cache_class():
             models keep working.  A folded layer (fuse_decode_(epilogues=True)) whose cache layer is a plain fp16 StaticLayer
             appends to it and attends over its valid rows with the HIP decode attention (runtime.rope_append_f16 /
             decode_attention_f16) instead -- and, with PREFILL_ATTENTION on, a prefill of more than 4 rows with
-            runtime.prefill_attention_f16; those paths ignore the attention mask, hence the unpadded-batch contract."""
+            runtime.prefill_attention_f16; those paths ignore the attention mask, hence the unpadded-batch contract.
+            kv_cache="fp8": every layer is a Kv8StaticLayer instead -- half the bytes, for folded layers only (DecodeSession checks)."""
 
-            def __init__(self, config, batch: int, max_cache_len: int, device, dtype):
+            def __init__(self, config, batch: int, max_cache_len: int, device, dtype, kv_cache: str = "fp16"):
                 super().__init__(config=config, max_cache_len=max_cache_len)
+                if kv_cache not in KV_CACHE_FORMATS:
+                    raise ValueError(f"DecodeCache: kv_cache must be one of {KV_CACHE_FORMATS}, not {kv_cache!r}")
+                self.kv_cache = kv_cache
+                if kv_cache == "fp8":
+                    if not all(type(lay) is StaticLayer for lay in self.layers):
+                        raise ValueError("DecodeCache: the FP8 cache replaces plain StaticLayers only (no sliding-window layers)")
+                    self.layers = [_kv8_layer_class()(max_cache_len=max_cache_len) for _ in self.layers]
                 text = config.get_text_config(decoder=True)
                 head_dim = getattr(text, "head_dim", None) or text.hidden_size // text.num_attention_heads
                 self.early_initialization(batch, text.num_key_value_heads, head_dim, dtype, torch.device(device))
@@ -151,15 +237,26 @@ class DecodeSession:
     token with nothing read on the host (run_selection reads the unfinished count every poll_every tokens).
 
     begin_speculation / step_speculate / run_speculation decode greedily 1 + K tokens per row and step (prompt-lookup speculative
-    decoding): the unit is "forward over the last token and K drafts, verify, draft" (runtime.spec_verify_f16), captured once."""
+    decoding): the unit is "forward over the last token and K drafts, verify, draft" (runtime.spec_verify_f16), captured once.
 
-    def __init__(self, model: nn.Module, batch: int, max_length: int, graph: bool = True):
+    kv_cache="fp8": the cache rows are FP8 with one power-of-two scale each (runtime.kv8_quantize), half the bytes of the fp16 cache.
+    Only the HIP entries of folded layers read such a cache, so the constructor raises ValueError -- naming the first condition that
+    fails -- unless every decoder layer is a fuse_decode_(epilogues=True) folded layer, the model is fp16, head_dim is 64 or 128,
+    batch <= 4 and max_length <= 65536.  Everything above works unchanged over it."""
+
+    def __init__(self, model: nn.Module, batch: int, max_length: int, graph: bool = True, kv_cache: str = "fp16"):
         if batch < 1 or max_length < 1:
             raise ValueError("DecodeSession: batch and max_length must be >= 1")
+        if kv_cache not in KV_CACHE_FORMATS:
+            raise ValueError(f"DecodeSession: kv_cache must be one of {KV_CACHE_FORMATS}, not {kv_cache!r}")
+        if kv_cache == "fp8":
+            why = _kv8_refusal(model, int(batch), int(max_length))
+            if why is not None:
+                raise ValueError(f'DecodeSession: kv_cache="fp8": {why}')
         emb = model.get_input_embeddings().weight
         self.model, self.batch, self.max_length, self.use_graph = model, int(batch), int(max_length), graph
-        self.device, self.dtype = emb.device, emb.dtype
-        self.cache = _decode_cache_class()(model.config, self.batch, self.max_length, self.device, self.dtype)
+        self.device, self.dtype, self.kv_cache = emb.device, emb.dtype, kv_cache
+        self.cache = _decode_cache_class()(model.config, self.batch, self.max_length, self.device, self.dtype, kv_cache=kv_cache)
         self._cols = torch.arange(self.max_length, device=self.device)
         self._bool_mask = model.config._attn_implementation == "sdpa"
         self.static_ids = torch.zeros(self.batch, 1, dtype=torch.long, device=self.device)
@@ -464,7 +561,7 @@ def _sampling_params(model: nn.Module, temperature=None, top_k=None, top_p=None)
 def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None = None, max_new_tokens: int | None = None,
              eos_token_id=None, pad_token_id: int | None = None, attention_mask: torch.Tensor | None = None, graph: bool = True,
              generator: torch.Generator | None = None, uniforms: torch.Tensor | None = None, poll_every: int = 8,
-             **kwargs) -> torch.Tensor:
+             kv_cache: str = "fp16", **kwargs) -> torch.Tensor:
     """Decoding of an unpadded batch input_ids [B, P] on the GPU: greedy -- what model.generate(input_ids, do_sample=False, ...)
     returns -- or, with do_sample=True, sampling with temperature / top_k / top_p (values not passed are resolved as model.generate
     resolves them: _sampling_params).  The result is the prompt followed by the new tokens, rows that met eos padded with
@@ -490,7 +587,12 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
     min(prompt_lookup_num_tokens, 4 // B - 1) tokens drafted from the row's own history, and keeps the drafts that the greedy choice
     confirms plus one more token: the greedy tokens, up to the effect of fp16 rounding on near-ties (a step of 1 + K rows and a step
     of one row round differently).  K < 1, logits that are not fp16, a shape the entries decline or K slack positions that would pass
-    max_position_embeddings: the one-token loop above.  With do_sample=True the call is handed to model.generate."""
+    max_position_embeddings: the one-token loop above.  With do_sample=True the call is handed to model.generate.
+
+    kv_cache="fp8": the session's cache rows are FP8 (DecodeSession(..., kv_cache="fp8"), which states what the model must be); the
+    argument is not forwarded to model.generate, which has no such cache, so a call that must be handed over raises ValueError."""
+    if kv_cache not in KV_CACHE_FORMATS:
+        raise ValueError(f"generate: kv_cache must be one of {KV_CACHE_FORMATS}, not {kv_cache!r}")
     sample = kwargs.get("do_sample", False) is True
     fixed = {k: v for k, v in _GREEDY_DEFAULTS.items() if not (sample and k == "do_sample")}
     known = set(_GREEDY_DEFAULTS) | set(_SAMPLING_ARGS if sample else _LOOKUP_ARGS)
@@ -502,6 +604,9 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
         native = T > 0 and top_k >= 0 and 0 < top_p <= 1 and model.get_input_embeddings().weight.dtype == torch.float16
 
     def hand_over():
+        if kv_cache != "fp16":
+            raise ValueError(f"generate: kv_cache={kv_cache!r} belongs to the decode loop on the GPU (an unpadded batch on a GPU model, "
+                             "greedy or temperature / top_k / top_p sampling); model.generate cannot honour it")
         if generator is not None or uniforms is not None:
             raise ValueError("generate: generator= and uniforms= belong to the sampling loop on the GPU (an unpadded batch on a GPU model "
                              "with fp16 logits, do_sample=True with temperature / top_k / top_p only); model.generate cannot honour them")
@@ -527,7 +632,7 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
         cap = getattr(getattr(model, "config", None), "max_position_embeddings", None)
         if model.get_input_embeddings().weight.dtype != torch.float16 or (cap is not None and total - 1 + K > cap):
             K = 0
-    sess = DecodeSession(model, B, total - 1 + K, graph=graph)
+    sess = DecodeSession(model, B, total - 1 + K, graph=graph, **({} if kv_cache == "fp16" else {"kv_cache": kv_cache}))
     logits = sess.prefill(input_ids)
     if K and logits.dtype == torch.float16 and runtime.spec_verify_ok(B, 1 + K, logits.shape[1]):
         sess.begin_speculation(input_ids, total, draft_tokens=K, max_ngram=min(ngram, runtime.SPEC_MAX_NGRAM), eos=eos, pad=pad, logits=logits)

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import runtime
-from .decoding import _decode_cache_layer, _prefill_cache_layer
+from .decoding import _decode_cache_layer, _kv8_cache_layer, _prefill_cache_layer
 from .packing import concat_rows
 from .quant import PBLinear, tensor_version
 
@@ -224,14 +224,16 @@ def _mlp_tail(down: PBLinear, act_fn, gu: torch.Tensor, inter: int, residual: to
     return y if residual is None else residual + y.reshape(residual.shape)
 
 
-def _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings):
+def _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings, kv8=None):
     """THE prefill-attention ladder of a folded layer (decoding.PREFILL_ATTENTION): more than 4 fp16 rows on the GPU without autograd,
     position_embeddings given, the layer not training and a DecodeCache layer that runtime.prefill_attention_ok takes -- else None,
     before anything ran, and the caller runs LlamaDecoderLayer.forward.  The layer as LlamaDecoderLayer / LlamaAttention compute it:
     the input norm, q / k / v through their modules (the GEMM kernels, as without the switch), RoPE in one launch (runtime.rope_f16,
     else HF's apply_rotary_pos_emb), the cache append and the causal attention over the valid rows (runtime.prefill_attention_f16,
     which advances the layer's position on the device as StaticLayer.update would have), o_proj, the residual, the post norm, the
-    MLP and the residual.  The attention mask is not used: DecodeCache's unpadded-batch contract."""
+    MLP and the residual.  The attention mask is not used: DecodeCache's unpadded-batch contract.
+    kv8: the layer's FP8 cache layer (decoding._kv8_cache_layer) -- the attention is then runtime.prefill_attention_kv8 whatever
+    PREFILL_ATTENTION says, and a shape it declines is an error: there is no other path over that cache."""
     x = hidden_states
     attn = self.self_attn
     if position_embeddings is None or x.dim() != 3 or x.shape[0] * x.shape[1] <= 4 or not x.is_cuda or x.dtype != torch.float16 \
@@ -240,7 +242,12 @@ def _prefill_layer_forward(self, hidden_states, past_key_values, position_embedd
     B, S, _ = x.shape
     D = attn.head_dim
     n_q, n_kv = attn.q_proj.out_features // D, attn.k_proj.out_features // D
-    lay = _prefill_cache_layer(past_key_values, attn.layer_idx, B, S, n_q, n_kv, D)
+    if kv8 is not None:
+        if not runtime.kv8_ok(B, S, n_q, n_kv, D, kv8.max_cache_len):
+            raise RuntimeError(f"the FP8 KV cache declines batch {B}, {S} rows, heads {n_q} / {n_kv} x {D} (runtime.kv8_ok)")
+        lay = kv8
+    else:
+        lay = _prefill_cache_layer(past_key_values, attn.layer_idx, B, S, n_q, n_kv, D)
     if lay is None:
         return None
     from transformers.models.llama import modeling_llama as ML
@@ -252,9 +259,13 @@ def _prefill_layer_forward(self, hidden_states, past_key_values, position_embedd
     if rot is None:
         rot = ML.apply_rotary_pos_emb(qk[:, :n_q * D].view(B, S, n_q, D).transpose(1, 2),
                                       qk[:, n_q * D:].view(B, S, n_kv, D).transpose(1, 2), cos, sin)
-    a = runtime.prefill_attention_f16(rot[0], rot[1], v, lay.keys, lay.values, lay.cumulative_length, attn.scaling)
-    if a is None:                           # (prefill_attention_ok held for the cache layer)
-        raise RuntimeError("prefill_attention_f16 declined a shape prefill_attention_ok took")
+    if kv8 is not None:
+        a = runtime.prefill_attention_kv8(rot[0], rot[1], v, lay.keys, lay.values, lay.key_scales, lay.value_scales,
+                                          lay.cumulative_length, attn.scaling)
+    else:
+        a = runtime.prefill_attention_f16(rot[0], rot[1], v, lay.keys, lay.values, lay.cumulative_length, attn.scaling)
+    if a is None:                           # (prefill_attention_ok / kv8_ok held for the cache layer)
+        raise RuntimeError("the prefill attention entry declined a shape its scope predicate took")
     h1 = x + attn.o_proj(a.view(B, S, -1))
     return h1 + self.mlp(self.post_attention_layernorm(h1))
 
@@ -266,12 +277,19 @@ def _folded_layer_forward(self, hidden_states, attention_mask=None, position_ids
     HF's cache update and attention interface, o_proj with the residual add in its store, the gate/up launch (RMSNorm prologue) and
     down_proj with the SwiGLU prologue and the residual add -- every step with HF's roundings, so the result equals the
     prologues=True layer's bit for bit.  More than 4 rows with decoding.PREFILL_ATTENTION on: _prefill_layer_forward (the HIP causal prefill attention over
-    a DecodeCache).  Every other call runs LlamaDecoderLayer.forward (the prologues=True layer)."""
+    a DecodeCache).  Every other call runs LlamaDecoderLayer.forward (the prologues=True layer).
+    Over an FP8 cache (DecodeSession(..., kv_cache="fp8")) the append and the attention are runtime.rope_append_kv8 +
+    decode_attention_kv8 at <= 4 rows and runtime.prefill_attention_kv8 above; a call that cannot take these paths (autograd,
+    training, not fp16, no position_embeddings) raises RuntimeError: LlamaDecoderLayer.forward cannot read that cache."""
     d_in = self.input_layernorm
+    kv8 = _kv8_cache_layer(past_key_values, self.self_attn.layer_idx)
     if position_embeddings is None or hidden_states.dim() != 3 or not _prologue_ok(hidden_states, d_in.norm.weight, stateless=True):
-        out = _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings)
+        out = _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings, kv8)
         if out is not None:
             return out
+        if kv8 is not None:
+            raise RuntimeError("a folded layer over an FP8 KV cache runs its HIP paths only: fp16 activations on the GPU, no autograd, "
+                               "eval mode and position_embeddings are required")
         return type(self).forward(self, hidden_states, attention_mask=attention_mask, position_ids=position_ids,
                                   past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings, **kwargs)
     from transformers.models.llama import modeling_llama as ML
@@ -288,7 +306,17 @@ def _folded_layer_forward(self, hidden_states, attention_mask=None, position_ids
     cos, sin = position_embeddings
     n_q, n_kv = (o_k - o_q) // D, (o_v - o_k) // D
     a = None
-    lay = _decode_cache_layer(past_key_values, attn.layer_idx, B, n_kv, D)
+    if kv8 is not None:
+        q = None if attn.training else runtime.rope_append_kv8(y, o_q, o_k, o_v, B, S, n_q, n_kv, D, cos, sin, kv8.keys, kv8.values,
+                                                               kv8.key_scales, kv8.value_scales, kv8.cumulative_length)
+        if q is None:
+            raise RuntimeError("a folded layer over an FP8 KV cache runs its HIP paths only: rope_append_kv8 declined this step "
+                               "(eval mode, head_dim 64 / 128, batch <= 4 and fp16 cos / sin are required)")
+        a = runtime.decode_attention_kv8(q, kv8.keys, kv8.values, kv8.key_scales, kv8.value_scales, kv8.cumulative_length, attn.scaling)
+        if a is None:
+            raise RuntimeError("decode_attention_kv8 declined a shape rope_append_kv8 took")
+        a = a.view(B, S, -1)
+    lay = None if kv8 is not None else _decode_cache_layer(past_key_values, attn.layer_idx, B, n_kv, D)
     if lay is not None and not attn.training:
         # DecodeSession's cache: RoPE + the cache append in one launch, then the HIP decode attention over the valid rows only; it
         # advances the layer's position on the device (StaticLayer.cumulative_length), as StaticLayer.update would have

@@ -322,6 +322,127 @@ def prefill_attention_f16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_c
     return out
 
 
+# ---- the FP8 KV cache (csrc/pbl_kv8.hip; the format is stated in include/pbl.h) -------------------------------------------------------
+KV8_E_MIN, KV8_E_MAX, KV8_MAX = -15, 7, 448.0
+
+
+def kv8_quantize(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The torch reference of the FP8 cache's row format (any device, CPU included): x [..., D] (the fp16 values the fp16 cache would
+    hold) -> (bytes uint8 [..., D], scale fp32 [...]).  Per row: amax = max |x|; e = the smallest integer with amax <= 448 * 2^e,
+    clamped to [-15, 7] (an all-zero row: -15); scale = 2^e; byte j = e4m3fn(x_j / 2^e), round to nearest even.  After the clamp at
+    e = 7 a row with amax > 57344 (+-inf included) saturates at +-448; a NaN element becomes a NaN byte and does not enter amax."""
+    xf = x.detach().float()
+    amax = torch.nan_to_num(xf.abs(), nan=0.0, posinf=float("inf")).amax(-1)
+    m, ex = torch.frexp(amax)                               # amax = m * 2^ex, m in [0.5, 1); 448 = 0.875 * 2^9
+    e = ex.to(torch.int32) - 9 + (m > 0.875).to(torch.int32)
+    e = torch.where(amax == 0, torch.full_like(e, KV8_E_MIN), e)
+    e = torch.where(torch.isinf(amax), torch.full_like(e, KV8_E_MAX), e).clamp(KV8_E_MIN, KV8_E_MAX)
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    y = (xf / scale[..., None]).clamp(-KV8_MAX, KV8_MAX)    # (exact: a power of two; NaN stays NaN)
+    return y.to(torch.float8_e4m3fn).view(torch.uint8), scale
+
+
+def kv8_dequantize(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """kv8_quantize's inverse on what it kept: bytes uint8 [..., D] and scale fp32 [...] -> fp16 [..., D], every value exact (a 4-bit
+    significand between 2^-24 and 57344 for scales the format allows)"""
+    return (q.view(torch.float8_e4m3fn).float() * scale[..., None].float()).to(torch.float16)
+
+
+def kv8_ok(batch: int, seq: int, n_q: int, n_kv: int, head_dim: int, max_len: int) -> bool:
+    """the scope of the FP8 cache's entries together: rope_append_kv8 + decode_attention_kv8 at seq <= 4 rows, prefill_attention_kv8
+    above -- head_dim 64 or 128, batch <= 4, n_kv dividing n_q, 1 <= seq <= max_len <= 65536"""
+    return head_dim in (64, 128) and 1 <= batch <= 4 and 1 <= seq <= max_len <= 65536 and n_kv >= 1 and n_q >= 1 and n_q % n_kv == 0
+
+
+def _cache_args_kv8(k_cache, v_cache, k_scale, v_scale, pos, device, what: str):
+    """_cache_args for the FP8 cache: [B, Hkv, max_len, D] uint8 k / v with [B, Hkv, max_len] fp32 scales, all contiguous on `device`"""
+    if k_cache.dtype != torch.uint8 or v_cache.dtype != torch.uint8 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape \
+            or not k_cache.is_contiguous() or not v_cache.is_contiguous() or k_cache.device != device or v_cache.device != device:
+        raise ValueError(f"{what}: k_cache / v_cache must be contiguous uint8 [B, Hkv, max_len, D] tensors on the activations' device")
+    for t in (k_scale, v_scale):
+        if t.dtype != torch.float32 or t.shape != k_cache.shape[:3] or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"{what}: k_scale / v_scale must be contiguous fp32 [B, Hkv, max_len] tensors on the activations' device")
+    if pos.dtype != torch.int64 or pos.numel() != 1 or pos.device != device:
+        raise ValueError(f"{what}: pos must be a one-element int64 tensor on the activations' device")
+    return tuple(int(d) for d in k_cache.shape)
+
+
+def rope_append_kv8(qkv: torch.Tensor, q_off: int, k_off: int, v_off: int, batch: int, seq: int, n_q: int, n_kv: int, head_dim: int,
+                    cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,
+                    v_scale: torch.Tensor, pos: torch.Tensor) -> torch.Tensor | None:
+    """rope_append_f16 over the FP8 cache (pbl_rope_append_kv8): the same q, bit for bit; the rotated k heads and the raw v heads are
+    quantised (kv8_quantize's rule) into rows [pos, pos + seq) of k_cache / v_cache [batch, n_kv, max_len, head_dim] uint8 and their
+    scales into k_scale / v_scale [batch, n_kv, max_len] fp32; pos is not changed.  None where rope_append_f16 returns None."""
+    form = _rope_form("rope_append_kv8", qkv, ((q_off, n_q), (k_off, n_kv), (v_off, n_kv)), batch, seq, head_dim, cos, sin)
+    B, Hkv, max_len, D = _cache_args_kv8(k_cache, v_cache, k_scale, v_scale, pos, qkv.device, "rope_append_kv8")
+    if (B, Hkv, D) != (batch, n_kv, head_dim):
+        raise ValueError("rope_append_kv8: the cache is not [batch, n_kv, max_len, head_dim]")
+    if form is None or not decode_attention_ok(batch, seq, n_q, n_kv, head_dim, max_len):
+        return None
+    (qs, qst), _ = _rope_layout(qkv, q_off, k_off, batch, seq, n_q, n_kv, head_dim, cos, sin)
+    if qst[3] != 1 or qs != (batch, n_q, seq, head_dim):
+        return None
+    q = torch.empty_strided(qs, qst, dtype=torch.float16, device=qkv.device)
+    rc = _lib.lib().pbl_rope_append_kv8(qkv.data_ptr(), form[0], q_off, k_off, v_off, batch, seq, n_q, n_kv, head_dim, *form[1],
+                                        q.data_ptr(), (C.c_int64 * 3)(*qst[:3]), k_cache.data_ptr(), v_cache.data_ptr(),
+                                        k_scale.data_ptr(), v_scale.data_ptr(), max_len, pos.data_ptr(),
+                                        torch.cuda.current_stream(qkv.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "rope + FP8 cache append")
+    return q
+
+
+def decode_attention_kv8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                         pos: torch.Tensor, scaling: float) -> torch.Tensor | None:
+    """decode_attention_f16 over the FP8 cache (pbl_decode_attn_kv8): bit for bit what decode_attention_f16 returns over
+    kv8_dequantize(k_cache, k_scale) / kv8_dequantize(v_cache, v_scale); advances pos by S.  None where that one returns None."""
+    if q.dim() != 4 or q.dtype != torch.float16 or not q.is_cuda or q.stride(3) != 1 or min(q.stride()) < 0:
+        raise ValueError("decode_attention_kv8: q must be an fp16 [B, Hq, S, D] GPU tensor with unit d stride")
+    B, Hq, S, D = (int(d) for d in q.shape)
+    Bc, Hkv, max_len, Dc = _cache_args_kv8(k_cache, v_cache, k_scale, v_scale, pos, q.device, "decode_attention_kv8")
+    if (Bc, Dc) != (B, D):
+        raise ValueError("decode_attention_kv8: the cache is not [B, Hkv, max_len, D] for q [B, Hq, S, D]")
+    if not decode_attention_ok(B, S, Hq, Hkv, D, max_len):
+        return None
+    L = _lib.lib()
+    out = torch.empty(B * S, Hq * D, dtype=torch.float16, device=q.device)
+    ws = torch.empty(int(L.pbl_decode_attn_workspace_bytes(B, S, Hq, D, max_len)), dtype=torch.uint8, device=q.device)
+    rc = L.pbl_decode_attn_kv8(q.data_ptr(), (C.c_int64 * 3)(*q.stride()[:3]), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                               v_scale.data_ptr(), B, S, Hq, Hkv, D, max_len, float(scaling), pos.data_ptr(), out.data_ptr(), Hq * D,
+                               ws.data_ptr(), ws.numel(), torch.cuda.current_stream(q.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "decode attention (FP8 cache)")
+    return out
+
+
+def prefill_attention_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                          k_scale: torch.Tensor, v_scale: torch.Tensor, pos: torch.Tensor, scaling: float) -> torch.Tensor | None:
+    """prefill_attention_f16 over the FP8 cache (pbl_prefill_attn_kv8): k / v are quantised into cache rows [pos, pos + S) and every
+    key and value is read back from there, so the result is bit for bit prefill_attention_f16's for k / v replaced by
+    kv8_dequantize(*kv8_quantize(.)) over an fp16 cache that holds the dequantised earlier rows; advances pos by S.  None where
+    prefill_attention_f16 returns None; the cache and pos are then untouched."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 4 or t.dtype != torch.float16 or not t.is_cuda or t.device != q.device or t.stride(3) != 1 or min(t.stride()) < 0:
+            raise ValueError(f"prefill_attention_kv8: {name} must be an fp16 [B, H, S, D] GPU tensor with unit d stride")
+    B, Hq, S, D = (int(d) for d in q.shape)
+    Bc, Hkv, max_len, Dc = _cache_args_kv8(k_cache, v_cache, k_scale, v_scale, pos, q.device, "prefill_attention_kv8")
+    if (Bc, Dc) != (B, D) or tuple(k.shape) != (B, Hkv, S, D) or k.shape != v.shape:
+        raise ValueError("prefill_attention_kv8: k / v must be [B, Hkv, S, D] and the cache [B, Hkv, max_len, D] for q [B, Hq, S, D]")
+    if not prefill_attention_ok(B, S, Hq, Hkv, D, max_len):
+        return None
+    out = torch.empty(B * S, Hq * D, dtype=torch.float16, device=q.device)
+    rc = _lib.lib().pbl_prefill_attn_kv8(q.data_ptr(), (C.c_int64 * 3)(*q.stride()[:3]), k.data_ptr(), (C.c_int64 * 3)(*k.stride()[:3]),
+                                         v.data_ptr(), (C.c_int64 * 3)(*v.stride()[:3]), k_cache.data_ptr(), v_cache.data_ptr(),
+                                         k_scale.data_ptr(), v_scale.data_ptr(), B, S, Hq, Hkv, D, max_len, float(scaling),
+                                         pos.data_ptr(), out.data_ptr(), Hq * D, torch.cuda.current_stream(q.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "prefill attention (FP8 cache)")
+    return out
+
+
 SELECT_MAX_VOCAB = 1 << 19
 
 
