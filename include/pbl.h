@@ -624,6 +624,39 @@ int pbl_select_token_f16(const void* logits, int64_t ld, int B, int V, float tem
                          int64_t n_steps, int64_t* step, const int64_t* eos, int n_eos, int64_t pad, uint8_t* unfinished,
                          int64_t* tokens, int64_t total, int64_t col0, int64_t* next_ids, int32_t* n_unfinished, int32_t* status,
                          uint8_t* kept, void* stream);
+/* pbl_select_token_f16 with one more filter behind top-p: min_p in [0, 1] (0: off; sampling only, ignored when u is NULL).
+ *     3a. a token kept so far stays iff exp(s_i - max s) >= min_p, in fp32 -- its probability relative to the top token's, which no
+ *         normaliser enters (HF's MinPLogitsWarper behind temperature, top-k and top-p); the maximum always stays.  kept reflects it.
+ * min_p outside [0, 1]: PBL_ERR_INVALID_ARG.  With min_p = 0 the entry does, bit for bit, what pbl_select_token_f16 does (which
+ * forwards here with 0). */
+int pbl_select_token_minp_f16(const void* logits, int64_t ld, int B, int V, float temperature, int top_k, float top_p, float min_p,
+                              const float* u, int64_t n_steps, int64_t* step, const int64_t* eos, int n_eos, int64_t pad,
+                              uint8_t* unfinished, int64_t* tokens, int64_t total, int64_t col0, int64_t* next_ids,
+                              int32_t* n_unfinished, int32_t* status, uint8_t* kept, void* stream);
+
+/* The logits processors of a decode step (csrc/pbl_logits.hip; harness.DecodeSession / harness.generate with repetition_penalty,
+ * no_repeat_ngram_size, min_new_tokens / min_length), in front of the selection: one launch, one workgroup per row, IN PLACE on
+ * logits [B, V] fp16 (row b at logits + b ld elements, ld >= V, any alignment).  HF runs its processors on an fp32 copy of the
+ * logits; the selection is defined on fp16 values, so the processed score is HF's fp32 result rounded to fp16 (nearest even).
+ *   tokens [B, total] int64, the result buffer of the selection; step, a DEVICE int64, read and left as it is.  The history of row b
+ *   is h = tokens[b, 0 : len), len = col0 + step clamped to [0, total]; ids outside [0, V) in h are skipped; every row is
+ *   processed, finished or not.  In HF's order:
+ *     1. repetition_penalty t (> 0; 1: off): for every DISTINCT id i in h, x = float(logit[i]), logit[i] = fp16(x < 0 ? x t : x / t),
+ *        fp32 with an IEEE division -- once per id, however often and wherever it occurs (every original is read into `scratch`
+ *        before the first store; all occurrences of an id then store the same bits: order-free);
+ *     2. no_repeat_ngram_size n (0: off; at most 8), len >= n: for every i in [0, len - n] with h[i : i + n - 1] ==
+ *        h[len - (n - 1) : len], logit[h[i + n - 1]] = -inf (n = 1: every id in h);
+ *     3. while step < min_new_tokens or col0 + step < min_length: logit[eos[j]] = -inf for every j < n_eos.
+ *   A barrier separates the rules: a ban wins over a penalty.  The same inputs give the same bits on every run.
+ *   scratch: [B, total] fp16 (may be NULL when repetition_penalty = 1), contents undefined afterwards.
+ * PBL_ERR_INVALID_ARG for NULL pointers (eos with n_eos = 0 may be NULL), sizes < 1, ld < V, col0 outside [0, total),
+ * repetition_penalty not > 0, no_repeat_ngram_size outside [0, 8] and logits or scratch overlapping an input or each other, before
+ * any device work; PBL_ERR_UNSUPPORTED for V > 524288 or total >= 2^31.  With every rule off (t = 1, n = 0, and no eos id or
+ * neither minimum able to hold) nothing is launched.  No allocation, no synchronisation, nothing read on the host: capturable in a
+ * hipGraph, and one captured graph serves every step. */
+int pbl_process_logits_f16(void* logits, int64_t ld, int B, int V, const int64_t* tokens, int64_t total, int64_t col0,
+                           const int64_t* step, float repetition_penalty, int no_repeat_ngram_size, int64_t min_new_tokens,
+                           int64_t min_length, const int64_t* eos, int n_eos, void* scratch, void* stream);
 
 /* Token scoring of an evaluation pass (csrc/pbl_score.hip; scoring.token_logprobs / scoring.loglikelihood / harness.perplexity(fused=
  * True)): per row of logits the log-probability of a target token and whether it is the arg-max, and per request the sum / AND over

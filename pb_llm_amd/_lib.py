@@ -63,6 +63,7 @@ EXPORTS = ["pbl_status_string", "pbl_version", "pbl_pack_dense_f32", "pbl_pack_d
            "pbl_gemm_f16_image_ws", "pbl_gemv_f16_fused_norm_host", "pbl_linear_f16_swiglu",
            "pbl_linear_f16_residual", "pbl_linear_f16_swiglu_residual", "pbl_rope_f16",
            "pbl_rope_append_f16", "pbl_decode_attn_workspace_bytes", "pbl_decode_attn_f16", "pbl_prefill_attn_f16", "pbl_select_token_f16",
+           "pbl_select_token_minp_f16", "pbl_process_logits_f16",
            "pbl_score_tokens_f16", "pbl_gemv_route", "pbl_spec_verify_f16", "pbl_ngram_draft",
            "pbl_rope_append_kv8", "pbl_decode_attn_kv8", "pbl_prefill_attn_kv8"]
 
@@ -256,6 +257,12 @@ def lib() -> C.CDLL:
     L.pbl_select_token_f16.restype = C.c_int
     L.pbl_select_token_f16.argtypes = [vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp, C.c_int64, vp, vp, C.c_int,
                                        C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
+    L.pbl_select_token_minp_f16.restype = C.c_int
+    L.pbl_select_token_minp_f16.argtypes = [vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, vp, C.c_int64, vp, vp,
+                                            C.c_int, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
+    L.pbl_process_logits_f16.restype = C.c_int
+    L.pbl_process_logits_f16.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_float, C.c_int, C.c_int64,
+                                         C.c_int64, vp, C.c_int, vp, vp]
     L.pbl_score_tokens_f16.restype = C.c_int
     L.pbl_score_tokens_f16.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     L.pbl_spec_verify_f16.restype = C.c_int

@@ -1,5 +1,5 @@
-// pbl_select.hip -- token selection of a decode step (pbl_select_token_f16): temperature, top-k, top-p, the draw, and the eos /
-// pad bookkeeping of a generation loop, on the device.
+// pbl_select.hip -- token selection of a decode step (pbl_select_token_f16, pbl_select_token_minp_f16): temperature, top-k, top-p,
+// min-p, the draw, and the eos / pad bookkeeping of a generation loop, on the device.
 //
 // One workgroup of 1024 threads per row of logits [B, V] fp16.  Everything is defined on VALUES, not on a sort order: an fp16 row
 // has at most 65536 distinct values, so a threshold is found by an MSB-first radix select over an order-preserving 16-bit key (12
@@ -45,7 +45,7 @@ struct SelArgs {
     int32_t* n_unfinished;
     int32_t* status;
     uint8_t* kept;                  // [B, V] or NULL
-    float temperature, top_p;
+    float temperature, top_p, min_p;
     int top_k, n_eos, B, V, vec, finish;
 };
 
@@ -64,6 +64,17 @@ __device__ __forceinline__ float sel_value(uint32_t key) {
 // the weight of a key as an integer: floor(2^44 exp(s - m)), s = value / temperature in fp32 (the key of the maximum gives 2^44)
 __device__ __forceinline__ u64 sel_weight(uint32_t key, float temperature, float m) {
     return u64(expf(sel_value(key) / temperature - m) * 0x1p44f);
+}
+
+// The weight of a key in the draw, 0 for a key that does not stay.  A key stays iff it passes the top-k / top-p cut and, with min_p > 0,
+// exp(s - max s) >= min_p -- its probability relative to the top one, which no normaliser enters: a rule on the value alone, on the
+// one exponential that is also the weight (the maximum gives exp(0) = 1 and always stays).  min_p = 0: sel_weight of the keys >= kcut.
+__device__ __forceinline__ u64 sel_kept_weight(uint32_t key, uint32_t kcut, float temperature, float m, float min_p, bool* keep) {
+    *keep = false;
+    if (key < kcut) return 0;                              // (no exponential for what top-k / top-p removed)
+    const float e = expf(sel_value(key) / temperature - m);
+    *keep = e >= min_p;                                    // (e >= 0 always: rows with a NaN are not sampled)
+    return *keep ? u64(e * 0x1p44f) : 0;
 }
 
 struct SelRow {
@@ -277,8 +288,8 @@ __global__ __launch_bounds__(SEL_THREADS) void pbl_select_token_kernel(SelArgs a
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if (k[j] != SEL_NONE) {
-                    const bool keep = k[j] >= kcut;
-                    if (keep) mine += sel_weight(k[j], a.temperature, m);
+                    bool keep;
+                    mine += sel_kept_weight(k[j], kcut, a.temperature, m, a.min_p, &keep);
                     if (a.kept) a.kept[int64_t(b) * a.V + i0 + j] = keep;
                 }
         });
@@ -312,8 +323,8 @@ __global__ __launch_bounds__(SEL_THREADS) void pbl_select_token_kernel(SelArgs a
                 sel_keys8(sel_load8(r, i0, end), i0, end, k);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const bool keep = k[j] != SEL_NONE && k[j] >= kcut;
-                    q[j] = keep ? sel_weight(k[j], a.temperature, m) : 0;
+                    bool keep;
+                    q[j] = k[j] != SEL_NONE ? sel_kept_weight(k[j], kcut, a.temperature, m, a.min_p, &keep) : 0;
                     sum += q[j];
                 }
                 const u64 incl = sel_wave_scan(sum);
@@ -378,14 +389,14 @@ bool sel_overlaps(const void* a, size_t na, const void* b, size_t nb) {
 
 extern "C" {
 
-int pbl_select_token_f16(const void* logits, int64_t ld, int B, int V, float temperature, int top_k, float top_p, const float* u,
-                         int64_t n_steps, int64_t* step, const int64_t* eos, int n_eos, int64_t pad, uint8_t* unfinished,
-                         int64_t* tokens, int64_t total, int64_t col0, int64_t* next_ids, int32_t* n_unfinished, int32_t* status,
-                         uint8_t* kept, void* stream) {
+int pbl_select_token_minp_f16(const void* logits, int64_t ld, int B, int V, float temperature, int top_k, float top_p, float min_p,
+                              const float* u, int64_t n_steps, int64_t* step, const int64_t* eos, int n_eos, int64_t pad,
+                              uint8_t* unfinished, int64_t* tokens, int64_t total, int64_t col0, int64_t* next_ids,
+                              int32_t* n_unfinished, int32_t* status, uint8_t* kept, void* stream) {
     if (!logits || !step || !unfinished || !tokens || !next_ids || !n_unfinished || !status || B < 1 || V < 1 || ld < V || total < 1 ||
         col0 < 0 || col0 >= total || n_eos < 0 || (n_eos > 0 && !eos) || (u && n_steps < 1))
         return PBL_ERR_INVALID_ARG;
-    if (!(temperature > 0.f) || !(top_p > 0.f && top_p <= 1.f) || top_k < 0) return PBL_ERR_INVALID_ARG;
+    if (!(temperature > 0.f) || !(top_p > 0.f && top_p <= 1.f) || top_k < 0 || !(min_p >= 0.f && min_p <= 1.f)) return PBL_ERR_INVALID_ARG;
     const void* ins[3] = {logits, u, eos};
     const size_t inb[3] = {size_t((int64_t(B) - 1) * ld + V) * 2, u ? size_t(n_steps) * B * 4 : 0, size_t(n_eos) * 8};
     const void* outs[7] = {step, unfinished, tokens, next_ids, n_unfinished, status, kept};
@@ -404,7 +415,7 @@ int pbl_select_token_f16(const void* logits, int64_t ld, int B, int V, float tem
     a.eos = eos; a.pad = pad;
     a.unfinished = unfinished; a.tokens = tokens; a.total = total; a.col0 = col0; a.next_ids = next_ids;
     a.n_unfinished = n_unfinished; a.status = status; a.kept = kept;
-    a.temperature = temperature; a.top_p = top_p; a.top_k = top_k; a.n_eos = n_eos; a.B = B; a.V = V;
+    a.temperature = temperature; a.top_p = top_p; a.min_p = min_p; a.top_k = top_k; a.n_eos = n_eos; a.B = B; a.V = V;
     a.vec = reinterpret_cast<uintptr_t>(logits) % 16 == 0 && (B == 1 || ld % 8 == 0);
     a.finish = B == 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -415,6 +426,14 @@ int pbl_select_token_f16(const void* logits, int64_t ld, int B, int V, float tem
     void* fargv[] = {&unfinished, &B, &n_unfinished, &step};
     return hipLaunchKernel(reinterpret_cast<const void*>(pbl_select_token_kernel_finish), dim3(1), dim3(64), fargv, 0, st) == hipSuccess
                ? PBL_OK : PBL_ERR_LAUNCH;
+}
+
+int pbl_select_token_f16(const void* logits, int64_t ld, int B, int V, float temperature, int top_k, float top_p, const float* u,
+                         int64_t n_steps, int64_t* step, const int64_t* eos, int n_eos, int64_t pad, uint8_t* unfinished,
+                         int64_t* tokens, int64_t total, int64_t col0, int64_t* next_ids, int32_t* n_unfinished, int32_t* status,
+                         uint8_t* kept, void* stream) {
+    return pbl_select_token_minp_f16(logits, ld, B, V, temperature, top_k, top_p, 0.f, u, n_steps, step, eos, n_eos, pad, unfinished, tokens,
+                                     total, col0, next_ids, n_unfinished, status, kept, stream);
 }
 
 }  // extern "C"

@@ -168,25 +168,39 @@ def _decode_cache_class():
 def _capture_graph(unit, device, restore=(), warmup: int = 2):
     """Warm `unit` up on a side stream (after every run the tensors in `restore` get their values back), then capture ONE run of it
     in a hipGraph -- the capture runs nothing.  Returns (graph, what unit returned under capture)"""
-    saved = [t.clone() for t in restore]
-    s = torch.cuda.Stream(device)
-    s.wait_stream(torch.cuda.current_stream(device))
-    with torch.cuda.stream(s), torch.no_grad():
-        for _ in range(warmup):
-            unit()
-            for t, v in zip(restore, saved):
-                t.copy_(v)
-    torch.cuda.current_stream(device).wait_stream(s)
-    torch.cuda.synchronize(device)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph), torch.no_grad():
-        out = unit()
+    # The collector stays off while the unit is warmed up and captured.  Seen once: the GPU test process aborted (SIGABRT, main thread,
+    # "Garbage-collecting" in the dump) at a pure-Python line of a forward over the FP8 cache, in a suite whose earlier tests had left
+    # torch.profiler results behind -- reference cycles of thousands of objects that only the collector frees.  The destructor that
+    # aborted was not identified and the abort was not reproduced; torch.cuda.graph does not collect before it captures any more, so a
+    # finaliser can run in the middle of a capture.  This closes that window at no cost (nothing is collected here).
+    import gc
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        saved = [t.clone() for t in restore]
+        s = torch.cuda.Stream(device)
+        s.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(s), torch.no_grad():
+            for _ in range(warmup):
+                unit()
+                for t, v in zip(restore, saved):
+                    t.copy_(v)
+        torch.cuda.current_stream(device).wait_stream(s)
+        torch.cuda.synchronize(device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph), torch.no_grad():
+            out = unit()
+    finally:
+        if was_enabled:
+            gc.enable()
     return graph, out
 
 
 @dataclass
 class _Selection:
-    """DecodeSession.begin_selection's state: prompt in columns [0, col0) of `tokens`, n tokens wanted, `done` so far; params (T, k, p)"""
+    """DecodeSession.begin_selection's state: prompt in columns [0, col0) of `tokens`, n tokens wanted, `done` so far; params (T, k, p);
+    processors (repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length) with `process`: whether one of them can act, i.e.
+    whether a step runs pbl_process_logits_f16 at all; `scratch` fp16 [batch, total] for the penalty"""
     tokens: torch.Tensor
     col0: int
     n: int
@@ -199,6 +213,10 @@ class _Selection:
     count: torch.Tensor
     status: torch.Tensor
     params: tuple[float, int, float]
+    min_p: float = 0.0
+    processors: tuple[float, int, int, int] = (1.0, 0, 0, 0)
+    process: bool = False
+    scratch: torch.Tensor | None = None
 
 
 @dataclass
@@ -232,9 +250,11 @@ class DecodeSession:
     max_length.
 
     prefill / step hand the logits back and leave the choice of the token to the caller.  begin_selection / select / step_select
-    keep the choice on the device as well (runtime.select_token_f16: greedy or temperature / top-k / top-p sampling, eos / pad
-    bookkeeping): the captured unit is then "forward over static_ids, select into static_ids", and a generation is one replay per
-    token with nothing read on the host (run_selection reads the unfinished count every poll_every tokens).
+    keep the choice on the device as well (runtime.select_token_f16: greedy or temperature / top-k / top-p / min-p sampling, eos /
+    pad bookkeeping): the captured unit is then "forward over static_ids, select into static_ids", and a generation is one replay per
+    token with nothing read on the host (run_selection reads the unfinished count every poll_every tokens).  A selection begun with
+    a repetition penalty, a no-repeat n-gram size or a minimum length runs runtime.process_logits_f16 on the logits in front of the
+    selection, inside the same unit; one begun without them launches exactly what it launched before they existed.
 
     begin_speculation / step_speculate / run_speculation decode greedily 1 + K tokens per row and step (prompt-lookup speculative
     decoding): the unit is "forward over the last token and K drafts, verify, draft" (runtime.spec_verify_f16), captured once.
@@ -311,13 +331,20 @@ class DecodeSession:
 
     # ---- token selection on the device
     def begin_selection(self, prompt: torch.Tensor, total: int, eos=(), pad: int | None = None, uniforms: torch.Tensor | None = None,
-                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
+                        no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, min_length: int = 0, min_p: float = 0.0) -> torch.Tensor:
         """Start a generation whose tokens are chosen on the device: allocates the result `tokens` [batch, total] (int64, the
         prompt [batch, P] in front, returned), the step counter, the rows' unfinished flags, their count and the status word.
         uniforms None: greedy; else fp32 [>= total - P, batch] uniforms in [0, 1), row t for the t-th new token, with temperature /
-        top_k (0 = off) / top_p (1 = off).  eos: ids that finish a row (finished rows receive `pad`)."""
+        top_k (0 = off) / top_p (1 = off) / min_p (0 = off).  eos: ids that finish a row (finished rows receive `pad`).
+        repetition_penalty (1 = off), no_repeat_ngram_size (0 = off, at most 8), min_new_tokens / min_length (eos ids blocked while
+        fewer than min_new_tokens new tokens or min_length tokens in all exist): HF's processors of those names, applied to the
+        logits by runtime.process_logits_f16 before every selection -- greedy or sampled; the penalty's scratch is allocated here."""
         if prompt.dim() != 2 or prompt.shape[0] != self.batch or not prompt.shape[1] < total:
             raise ValueError(f"DecodeSession.begin_selection: prompt must be [{self.batch}, P < total]")
+        if not repetition_penalty > 0 or not 0 <= no_repeat_ngram_size <= runtime.PROCESS_MAX_NGRAM or not 0 <= min_p <= 1:
+            raise ValueError(f"DecodeSession.begin_selection: repetition_penalty > 0, 0 <= no_repeat_ngram_size <= "
+                             f"{runtime.PROCESS_MAX_NGRAM} and 0 <= min_p <= 1")
         dev, P = self.device, int(prompt.shape[1])
         if uniforms is not None:
             if uniforms.dim() != 2 or uniforms.shape[0] < total - P or uniforms.shape[1] != self.batch:
@@ -330,19 +357,33 @@ class DecodeSession:
                               eos=torch.tensor(eos, dtype=torch.long, device=dev) if eos else None,
                               step=torch.zeros(1, dtype=torch.long, device=dev), unfinished=torch.ones(self.batch, dtype=torch.bool, device=dev),
                               count=torch.full((1,), self.batch, dtype=torch.int32, device=dev),
-                              status=torch.zeros(1, dtype=torch.int32, device=dev), params=(float(temperature), int(top_k), float(top_p)))
-        self.sel_graph = None                                  # a captured unit holds the previous selection's tensors and parameters
+                              status=torch.zeros(1, dtype=torch.int32, device=dev), params=(float(temperature), int(top_k), float(top_p)),
+                              min_p=float(min_p))
+        theta, ngram, min_new, min_len = float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens), int(min_length)
+        c = self.sel
+        c.processors = (theta, ngram, min_new, min_len)
+        c.process = theta != 1.0 or ngram > 0 or (bool(eos) and (min_new > 0 or min_len > P))
+        if theta != 1.0:
+            c.scratch = torch.empty(self.batch, total, dtype=torch.float16, device=dev)
+        self.sel_graph = None                                 # a captured unit holds the previous selection's tensors and parameters
         return tokens
 
     @torch.no_grad()
     def select(self, logits: torch.Tensor) -> None:
         """choose the next token of every row from `logits` [batch, vocab] fp16 on the device: it lands in the result, in static_ids
-        (the next step's input) and in the bookkeeping of begin_selection.  A missing kernel is an error, not a fallback."""
+        (the next step's input) and in the bookkeeping of begin_selection.  With processors (begin_selection) the logits are
+        rewritten IN PLACE first.  A missing kernel is an error, not a fallback."""
         c = self.sel
         T, k, p = c.params
+        if c.process:
+            theta, ngram, min_new, min_len = c.processors
+            if logits.dtype != torch.float16 or runtime.process_logits_f16(
+                    logits, c.tokens, c.col0, c.step, repetition_penalty=theta, no_repeat_ngram_size=ngram, min_new_tokens=min_new,
+                    min_length=min_len, eos=c.eos, scratch=c.scratch) is None:
+                raise ValueError("DecodeSession.select: pbl_process_logits_f16 declines these logits (runtime.process_logits_ok)")
         if runtime.select_token_f16(logits, c.step, c.unfinished, c.tokens, c.col0, self.static_ids, c.count, c.status,
-                                    temperature=T, top_k=k, top_p=p, uniforms=c.uniforms, eos=c.eos, pad=c.pad) is None:
-            raise ValueError("DecodeSession.select: pbl_select_token_f16 declines these logits (runtime.select_token_ok)")
+                                    temperature=T, top_k=k, top_p=p, uniforms=c.uniforms, eos=c.eos, pad=c.pad, min_p=c.min_p) is None:
+            raise ValueError("DecodeSession.select: pbl_select_token_minp_f16 declines these logits (runtime.select_token_ok)")
 
     def _unit(self):
         self.select(self._forward(self.static_ids))
@@ -540,6 +581,7 @@ def _generation_limits(model: nn.Module, prompt_len: int, max_length=None, max_n
 
 _GREEDY_DEFAULTS = {"do_sample": False, "num_beams": 1, "use_cache": True}
 _SAMPLING_ARGS = ("temperature", "top_k", "top_p")
+_PROCESSOR_ARGS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "min_length")   # greedy and sampled; min_p: sampled
 _LOOKUP_ARGS = ("prompt_lookup_num_tokens", "max_matching_ngram_size")      # greedy only: prompt-lookup speculative decoding
 
 
@@ -557,19 +599,43 @@ def _sampling_params(model: nn.Module, temperature=None, top_k=None, top_p=None)
     return float(vals[0]), int(vals[1]), float(vals[2])
 
 
+def _processor_params(model: nn.Module, prompt_len: int, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None,
+                      min_length=None, min_p=None) -> tuple[float, int, int, int, float]:
+    """(repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, min_p) as model.generate resolves them for a prompt
+    of prompt_len tokens: the argument, else the value in model.generation_config, else transformers' default (_sampling_params'
+    rule; min_new_tokens and min_p have none and stay off).  A min_new_tokens that is set replaces min_length by prompt_len +
+    min_new_tokens, as _prepare_generated_length does.  1.0 / 0 / 0 / 0 / 0.0 mean "off" (HF builds no processor for them; it
+    builds the two length processors only with an eos id, and the min_p warper only for do_sample=True)."""
+    from transformers import GenerationConfig
+    gc = getattr(model, "generation_config", None)
+    defaults = GenerationConfig._get_default_generation_params()
+    vals = {}
+    for name, v in (("repetition_penalty", repetition_penalty), ("no_repeat_ngram_size", no_repeat_ngram_size),
+                    ("min_new_tokens", min_new_tokens), ("min_length", min_length), ("min_p", min_p)):
+        v = getattr(gc, name, None) if v is None else v
+        vals[name] = defaults.get(name) if v is None else v
+    if vals["min_new_tokens"] is not None:
+        vals["min_length"] = int(vals["min_new_tokens"]) + prompt_len
+    return (float(vals["repetition_penalty"]), int(vals["no_repeat_ngram_size"]), int(vals["min_new_tokens"] or 0),
+            int(vals["min_length"] or 0), float(vals["min_p"] or 0.0))
+
+
 @torch.no_grad()
 def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None = None, max_new_tokens: int | None = None,
              eos_token_id=None, pad_token_id: int | None = None, attention_mask: torch.Tensor | None = None, graph: bool = True,
              generator: torch.Generator | None = None, uniforms: torch.Tensor | None = None, poll_every: int = 8,
              kv_cache: str = "fp16", **kwargs) -> torch.Tensor:
     """Decoding of an unpadded batch input_ids [B, P] on the GPU: greedy -- what model.generate(input_ids, do_sample=False, ...)
-    returns -- or, with do_sample=True, sampling with temperature / top_k / top_p (values not passed are resolved as model.generate
-    resolves them: _sampling_params).  The result is the prompt followed by the new tokens, rows that met eos padded with
-    pad_token_id, ending where every row has finished or at the length limit.  One DecodeSession: the prompt is prefilled eagerly,
-    then each token replays ONE captured unit -- the decode step and the HIP token selection (pbl_select_token_f16), which writes
-    the token into the result and into the next step's input and keeps the eos / pad bookkeeping on the device.  The host reads
-    the count of unfinished rows every `poll_every` tokens (never without an eos id); tokens generated after every row finished
-    are pad and are cut off, so the result does not depend on poll_every.
+    returns -- or, with do_sample=True, sampling with temperature / top_k / top_p / min_p (values not passed are resolved as
+    model.generate resolves them: _sampling_params, _processor_params).  repetition_penalty, no_repeat_ngram_size (at most 8) and
+    min_new_tokens / min_length act in both modes, on the device too (pbl_process_logits_f16 in front of the selection, inside the
+    captured unit; HF's fp32 result rounded to fp16) -- also when only the model's generation_config sets them.  The result is the
+    prompt followed by the new tokens, rows that met eos padded with pad_token_id, ending where every row has finished or at the
+    length limit.  One DecodeSession: the prompt is prefilled eagerly, then each token replays ONE captured unit -- the decode step
+    and the HIP token selection (pbl_select_token_minp_f16), which writes the token into the result and into the next step's input
+    and keeps the eos / pad bookkeeping on the device.  The host reads the count of unfinished rows every `poll_every` tokens (never
+    without an eos id); tokens generated after every row finished are pad and are cut off, so the result does not depend on
+    poll_every.
 
     Sampling draws its uniforms ONCE per call, before the loop: torch.rand([new tokens, B]) from `generator` (default: the default
     generator of the model's device, so torch.manual_seed(n) reproduces a run), or the caller's table `uniforms` [>= new tokens, B]
@@ -578,9 +644,12 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
     up to HF's arbitrary choice inside a block of tied values at the top-p boundary.
 
     Handed to model.generate unchanged: an attention_mask with zeros (a padded batch), a model off the GPU, beams, any other
-    generation argument (repetition_penalty, min_p, ...), do_sample=False together with sampling arguments, and sampling on a model
-    whose logits are not fp16.  model.generate cannot honour `generator` or `uniforms`, so a call that passes one of them and must
-    be handed over raises ValueError.  Greedy decoding of logits that are not fp16 keeps the selection in torch.
+    generation argument (typical_p, bad_words_ids, ...), do_sample=False together with sampling arguments (min_p among them),
+    sampling or logits processors on a model whose logits are not fp16, no_repeat_ngram_size > 8, values HF itself refuses (it
+    raises), and logits processors together with prompt_lookup_num_tokens (the verify kernel takes the raw arg-max).  A minimum
+    length without an eos id processes nothing (HF builds no processor) and hands nothing over.  model.generate cannot honour
+    `generator` or `uniforms`, so a call that passes one of them and must be handed over raises ValueError.  Greedy decoding of
+    logits that are not fp16 keeps the selection in torch.
 
     prompt_lookup_num_tokens (with max_matching_ngram_size, default 2, at most 4 here), greedy decoding only: prompt-lookup speculative
     decoding on the device (DecodeSession.begin_speculation / run_speculation).  Each step feeds the last token and K =
@@ -595,21 +664,30 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
         raise ValueError(f"generate: kv_cache must be one of {KV_CACHE_FORMATS}, not {kv_cache!r}")
     sample = kwargs.get("do_sample", False) is True
     fixed = {k: v for k, v in _GREEDY_DEFAULTS.items() if not (sample and k == "do_sample")}
-    known = set(_GREEDY_DEFAULTS) | set(_SAMPLING_ARGS if sample else _LOOKUP_ARGS)
+    known = set(_GREEDY_DEFAULTS) | set(_SAMPLING_ARGS + ("min_p",) if sample else _LOOKUP_ARGS) | set(_PROCESSOR_ARGS)
     native = all(kwargs[k] == v for k, v in fixed.items() if k in kwargs) and not set(kwargs) - known
     padded = attention_mask is not None and not bool(attention_mask.all())
     T, top_k, top_p = 1.0, 0, 1.0                          # greedy: everything off
     if native and sample:
         T, top_k, top_p = _sampling_params(model, *(kwargs.get(k) for k in _SAMPLING_ARGS))
         native = T > 0 and top_k >= 0 and 0 < top_p <= 1 and model.get_input_embeddings().weight.dtype == torch.float16
+    theta, no_repeat, min_new, min_len, min_p = 1.0, 0, 0, 0, 0.0
+    if native and input_ids.dim() == 2:
+        theta, no_repeat, min_new, min_len, min_p = _processor_params(
+            model, input_ids.shape[1], *(kwargs.get(k) for k in _PROCESSOR_ARGS), kwargs.get("min_p") if sample else None)
+        if not sample:
+            min_p = 0.0                                        # HF builds warpers for do_sample=True only
+        if not (theta > 0 and 0 <= no_repeat <= runtime.PROCESS_MAX_NGRAM and 0 <= min_p <= 1):
+            native = False                                     # HF's own errors, or an n-gram size beyond the kernel's
 
     def hand_over():
         if kv_cache != "fp16":
             raise ValueError(f"generate: kv_cache={kv_cache!r} belongs to the decode loop on the GPU (an unpadded batch on a GPU model, "
-                             "greedy or temperature / top_k / top_p sampling); model.generate cannot honour it")
+                             "greedy or temperature / top_k / top_p / min_p sampling); model.generate cannot honour it")
         if generator is not None or uniforms is not None:
             raise ValueError("generate: generator= and uniforms= belong to the sampling loop on the GPU (an unpadded batch on a GPU model "
-                             "with fp16 logits, do_sample=True with temperature / top_k / top_p only); model.generate cannot honour them")
+                             "with fp16 logits, do_sample=True with temperature / top_k / top_p / min_p and the logits processors "
+                             "of _processor_params only); model.generate cannot honour them")
         hf = dict(kwargs)
         for k, v in (("max_length", max_length), ("max_new_tokens", max_new_tokens), ("eos_token_id", eos_token_id),
                      ("pad_token_id", pad_token_id), ("attention_mask", attention_mask)):
@@ -623,6 +701,10 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
         raise ValueError("generate: poll_every must be >= 1")
     B, P = input_ids.shape
     total, eos, pad = _generation_limits(model, P, max_length, max_new_tokens, eos_token_id, pad_token_id)
+    # whether a step would process anything -- begin_selection's rule: HF builds the two length processors only with an eos id
+    processing = theta != 1.0 or no_repeat > 0 or (bool(eos) and (min_new > 0 or min_len > P))
+    if processing and (kwargs.get("prompt_lookup_num_tokens") is not None or model.get_input_embeddings().weight.dtype != torch.float16):
+        return hand_over()                                 # the verify kernel takes the raw arg-max; the kernel takes fp16 logits
     K = 0
     if kwargs.get("prompt_lookup_num_tokens") is not None:
         lookup, ngram = int(kwargs["prompt_lookup_num_tokens"]), int(kwargs.get("max_matching_ngram_size") or 2)
@@ -646,12 +728,14 @@ def generate(model: nn.Module, input_ids: torch.Tensor, max_length: int | None =
             else:                                          # one draw for the whole call; a host generator draws on the host
                 gdev = generator.device if generator is not None else input_ids.device
                 table = torch.rand(total - P, B, generator=generator, device=gdev, dtype=torch.float32)
-        sess.begin_selection(input_ids, total, eos=eos, pad=pad, uniforms=table, temperature=T, top_k=top_k, top_p=top_p)
+        sess.begin_selection(input_ids, total, eos=eos, pad=pad, uniforms=table, temperature=T, top_k=top_k, top_p=top_p,
+                             repetition_penalty=theta, no_repeat_ngram_size=no_repeat, min_new_tokens=min_new, min_length=min_len,
+                             min_p=min_p)
         sess.select(logits)
         sess.sel.done = 1
         sess.run_selection(total - P - 1, poll_every)
         return sess.selection_result()
-    if sample:
+    if sample or processing:
         return hand_over()
     out = [input_ids]
     eos_t = torch.tensor(eos, dtype=input_ids.dtype, device=input_ids.device) if eos else None

@@ -454,7 +454,7 @@ def select_token_ok(batch: int, vocab: int) -> bool:
 def select_token_f16(logits: torch.Tensor, step: torch.Tensor, unfinished: torch.Tensor, tokens: torch.Tensor, col0: int,
                      next_ids: torch.Tensor, n_unfinished: torch.Tensor, status: torch.Tensor, temperature: float = 1.0,
                      top_k: int = 0, top_p: float = 1.0, uniforms: torch.Tensor | None = None, eos: torch.Tensor | None = None,
-                     pad: int = 0, kept: torch.Tensor | None = None) -> bool | None:
+                     pad: int = 0, kept: torch.Tensor | None = None, min_p: float = 0.0) -> bool | None:
     """One token per row of logits [B, V] fp16 (unit column stride; the view out.logits[:, -1] is fine), chosen and booked on the
     device in one call (pbl_select_token_f16; the rules are in include/pbl.h): greedy when `uniforms` is None, else temperature /
     top_k (0 = off) / top_p (1 = off) sampling with the uniform uniforms[step, b] (fp32 [n_steps, B], values in [0, 1)).  All state
@@ -462,7 +462,8 @@ def select_token_f16(logits: torch.Tensor, step: torch.Tensor, unfinished: torch
     column col0 + step receives the token), next_ids (int64, B elements: the next step's input), n_unfinished and status (int32,
     one element each; status bit 0: a sampled row held NaN / +inf, bit 1: step out of range), eos (int64 ids or None), kept
     (optional uint8 [B, V]: the mask of tokens that survived the filters).  Nothing is read on the host and nothing allocated:
-    capturable in a hipGraph.  True when it ran, None where the entry declines (select_token_ok)."""
+    capturable in a hipGraph.  True when it ran, None where the entry declines (select_token_ok).  min_p (0 = off, sampling only):
+    behind top_k and top_p a token stays only if exp(s - max s) >= min_p (pbl_select_token_minp_f16; with 0 the same result bit for bit)."""
     def dev(t, dtypes, n=None):
         return t.is_cuda and t.device == logits.device and t.dtype in dtypes and t.is_contiguous() and (n is None or t.numel() == n)
 
@@ -483,13 +484,13 @@ def select_token_f16(logits: torch.Tensor, step: torch.Tensor, unfinished: torch
         raise ValueError("select_token_f16: eos must be a 1-D int64 tensor on the logits' device")
     if kept is not None and not dev(kept, flags, B * V):
         raise ValueError("select_token_f16: kept must be a contiguous uint8 [B, V] tensor on the logits' device")
-    if not temperature > 0 or top_k < 0 or not 0 < top_p <= 1:
-        raise ValueError("select_token_f16: temperature > 0, top_k >= 0 and 0 < top_p <= 1")
+    if not temperature > 0 or top_k < 0 or not 0 < top_p <= 1 or not 0 <= min_p <= 1:
+        raise ValueError("select_token_f16: temperature > 0, top_k >= 0, 0 < top_p <= 1 and 0 <= min_p <= 1")
     if not select_token_ok(B, V):
         return None
     n_eos = 0 if eos is None else int(eos.numel())
-    rc = _lib.lib().pbl_select_token_f16(
-        logits.data_ptr(), logits.stride(0) if B > 1 else V, B, V, float(temperature), int(top_k), float(top_p),
+    rc = _lib.lib().pbl_select_token_minp_f16(
+        logits.data_ptr(), logits.stride(0) if B > 1 else V, B, V, float(temperature), int(top_k), float(top_p), float(min_p),
         None if uniforms is None else uniforms.data_ptr(), 0 if uniforms is None else int(uniforms.shape[0]), step.data_ptr(),
         eos.data_ptr() if n_eos else None, n_eos, int(pad), unfinished.data_ptr(), tokens.data_ptr(), int(tokens.shape[1]), int(col0),
         next_ids.data_ptr(), n_unfinished.data_ptr(), status.data_ptr(), None if kept is None else kept.data_ptr(),
@@ -497,6 +498,56 @@ def select_token_f16(logits: torch.Tensor, step: torch.Tensor, unfinished: torch
     if rc == _lib.PBL_ERR_UNSUPPORTED:
         return None
     _lib.check(rc, "token selection")
+    return True
+
+
+PROCESS_MAX_NGRAM = 8
+
+
+def process_logits_ok(batch: int, vocab: int, total: int = 1) -> bool:
+    """the scope of process_logits_f16 (pbl_process_logits_f16): select_token_f16's, and a result buffer of fewer than 2^31 columns"""
+    return select_token_ok(batch, vocab) and 1 <= total < (1 << 31)
+
+
+def process_logits_f16(logits: torch.Tensor, tokens: torch.Tensor, col0: int, step: torch.Tensor, repetition_penalty: float = 1.0,
+                       no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, min_length: int = 0, eos: torch.Tensor | None = None,
+                       scratch: torch.Tensor | None = None) -> bool | None:
+    """The logits processors of a decode step, IN PLACE on logits [B, V] fp16 (unit column stride, any row stride and alignment) on
+    the device in one launch (pbl_process_logits_f16; the rules are in include/pbl.h), over the history tokens[b, :col0 + step] of
+    every row: repetition_penalty (> 0, 1 = off; once per distinct id), no_repeat_ngram_size (0 = off, at most 8: -inf for every token
+    that would complete an n-gram the history holds) and, while step < min_new_tokens or col0 + step < min_length, -inf for the eos
+    ids.  The result is what HF's processors give on an fp32 copy, rounded to fp16.  tokens (int64 [B, total]), step (int64, one
+    element; read, not advanced) and eos (int64 ids or None) are select_token_f16's; scratch: a contiguous fp16 [B, total] tensor,
+    needed with a penalty.  Nothing is read on the host and nothing allocated: capturable in a hipGraph.  True when it ran, None where
+    the entry declines (process_logits_ok)."""
+    def dev(t, dtypes, n=None):
+        return t.is_cuda and t.device == logits.device and t.dtype in dtypes and t.is_contiguous() and (n is None or t.numel() == n)
+
+    if not logits.is_cuda or logits.dim() != 2 or logits.dtype != torch.float16 or logits.stride(1) != 1 or logits.shape[1] < 1 \
+            or logits.shape[0] < 1 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        raise ValueError("process_logits_f16: logits must be an fp16 [B, V] GPU tensor with unit column stride")
+    B, V = (int(d) for d in logits.shape)
+    if not dev(step, (torch.int64,), 1):
+        raise ValueError("process_logits_f16: step must be a contiguous int64 tensor of one element on the logits' device")
+    if not dev(tokens, (torch.int64,)) or tokens.dim() != 2 or tokens.shape[0] != B or not 0 <= col0 < tokens.shape[1]:
+        raise ValueError("process_logits_f16: tokens must be a contiguous int64 [B, total] tensor on the logits' device, 0 <= col0 < total")
+    if eos is not None and (not dev(eos, (torch.int64,)) or eos.dim() != 1):
+        raise ValueError("process_logits_f16: eos must be a 1-D int64 tensor on the logits' device")
+    if not repetition_penalty > 0 or not 0 <= no_repeat_ngram_size <= PROCESS_MAX_NGRAM:
+        raise ValueError(f"process_logits_f16: repetition_penalty > 0 and 0 <= no_repeat_ngram_size <= {PROCESS_MAX_NGRAM}")
+    total = int(tokens.shape[1])
+    if float(repetition_penalty) != 1.0 and (scratch is None or not dev(scratch, (torch.float16,), B * total)):
+        raise ValueError("process_logits_f16: a repetition penalty needs scratch, a contiguous fp16 [B, total] tensor on the logits' device")
+    if not process_logits_ok(B, V, total):
+        return None
+    n_eos = 0 if eos is None else int(eos.numel())
+    rc = _lib.lib().pbl_process_logits_f16(
+        logits.data_ptr(), logits.stride(0) if B > 1 else V, B, V, tokens.data_ptr(), total, int(col0), step.data_ptr(),
+        float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens), int(min_length), eos.data_ptr() if n_eos else None, n_eos,
+        None if scratch is None else scratch.data_ptr(), torch.cuda.current_stream(logits.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "logits processing")
     return True
 
 
