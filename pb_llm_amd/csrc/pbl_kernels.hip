@@ -350,6 +350,25 @@ __device__ __forceinline__ void stage_row(_Float16* dst, const uint16_t* a, cons
     for (int i = K + tid; i < xstride; i += NTHR) dst[i] = _Float16(0);
 }
 
+// s_waitcnt vmcnt(N) alone (gfx9 encoding: vmcnt in bits 3:0 and 15:14; expcnt, bits 6:4, and lgkmcnt, bits 11:8, left at their
+// maxima): returns once at most N of this wave's vector-memory requests are outstanding; loads retire in issue order.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    static_assert(N >= 0 && N < 16, "one field");
+    __builtin_amdgcn_s_waitcnt(0x0F70 | N);
+}
+
+// Tile register sets of pbl_gemv_kernel's sign phase: 3 = a static ring, a tile is requested two panels before its use; 2 = two
+// registers rotated, one panel.  The ring costs the kernel 12 VGPRs (56 -> 68: off the 64 step), so only the instantiation it
+// was measured on takes it: the one-token code-mode kernel of the grouped decode launch, fp16 activations, no prologue or
+// epilogue.  Not the split kernels either: a wave strides WSTEP panels, the ring's first loop needs more than 4 WSTEP of them,
+// and no layer has 17 (SPLIT = 4) or 33 (SPLIT = 8) panels.  Every other instantiation keeps the rotation and with it the
+// machine code it had (profiles/r16_gemv_lookahead.md).
+template <int MB, bool SF, int SPLIT, bool XB, int XP>
+constexpr int gemv_tile_sets() {
+    return MB == 1 && !SF && SPLIT == 1 && !XB && XP == 0 ? 3 : 2;
+}
+
 // SPLIT == 1: each of the WPB waves of a workgroup owns its own record (throughput mode, the
 // L-layer stream).  SPLIT > 1 (== WPB): the waves of a workgroup COOPERATE on one record --
 // wave w takes panels w, w+S, ... and salient rounds w, w+S, ... and the partial sums are
@@ -426,6 +445,7 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs ar
     const uint32_t off_sal = tiles_off + uint32_t(P) * 1024u;
     const uint32_t nchu = uint32_t(nch);
 
+    constexpr int D = gemv_tile_sets<MB, SF, SPLIT, XB, XP>();
     const u32x4* tiles = reinterpret_cast<const u32x4*>(rec + tiles_off) + lane;
     const uint8_t* sal = rec + off_sal;
     const uint16_t* col0p = reinterpret_cast<const uint16_t*>(sal);
@@ -433,9 +453,24 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs ar
     const u32x4* codep = reinterpret_cast<const u32x4*>(sal + PBL_SAL_CODE_OFF(nchu));
     const uint8_t* tailcnt = sal + PBL_SAL_TAILCNT_OFF(nchu);
 
-    // Two tile registers, rotated in phase 1 (t0 <- t1 <- the panel two steps on), and this wave's first salient round.  The
-    // weight stream is read once: every load of it is non-temporal.
+    // The tile registers of phase 1, of which the first two are requested here, and this wave's first salient round.  The weight
+    // stream is read once: every load of it is non-temporal.  D = 2: two registers, rotated (t0 <- t1 <- the panel two steps on).
+    // D = 3: a ring of three sets, panel number n of this wave computes from set n % 3; a tile load takes a wave-uniform base (the
+    // panel's 1 KiB, an SGPR pair) and ONE 32-bit lane offset, as the salient loads do.  (Two declarations, of which an
+    // instantiation uses one -- t0 / t1 at D = 2, t[] at D = 3 -- and the other is dead and allocates nothing: as elements of t[]
+    // hipcc splits the rotated registers into words and waits for the second tile here, in front of phase 0.)
     u32x4 t0 = {0, 0, 0, 0}, t1 = {0, 0, 0, 0};
+    u32x4 t[3];
+    t[0] = u32x4{0, 0, 0, 0}; t[1] = u32x4{0, 0, 0, 0};
+    uint32_t lane16 = uint32_t(lane) * 16u;
+    const uint8_t* tile0 = rec + tiles_off;     // (a local of its own: with rec + tiles_off inside the lambda every load goes flat)
+    auto tile_fetch = [&](int p) {
+        // both offsets opaque per request: else hipcc hoists the lane's address out of the loop as a 64-bit VGPR base, or folds the
+        // panel's offset into an immediate that overflows at the fourth KiB and falls back to a 64-bit VGPR address
+        size_t off = size_t(uint32_t(p)) * 1024u;
+        asm volatile("" : "+s"(off), "+v"(lane16));
+        return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(tile0 + off + size_t(lane16)));
+    };
     // One salient round's loads: chunk min(c, nch - 1) of the three streams.  The bases are wave-uniform and the chunk index is
     // unsigned, so each load takes an SGPR base and ONE 32-bit lane offset (no 64-bit address arithmetic per round).
     auto sal_fetch = [&](int c, uint32_t& c0, u32x4& d4, u32x4& q4) {
@@ -447,8 +482,13 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs ar
     uint32_t s_c0 = 0;
     u32x4 s_d4 = {0, 0, 0, 0}, s_q4 = {0, 0, 0, 0};
     if (active) {
-        if (wslot < P) t0 = __builtin_nontemporal_load(tiles + wslot * 64);
-        if (wslot + WSTEP < P) t1 = __builtin_nontemporal_load(tiles + (wslot + WSTEP) * 64);
+        if constexpr (D == 2) {
+            if (wslot < P) t0 = __builtin_nontemporal_load(tiles + wslot * 64);
+            if (wslot + WSTEP < P) t1 = __builtin_nontemporal_load(tiles + (wslot + WSTEP) * 64);
+        } else {
+            if (wslot < P) t[0] = tile_fetch(wslot);
+            if (wslot + WSTEP < P) t[1] = tile_fetch(wslot + WSTEP);
+        }
         if (nch > wslot * PBL_WAVE) sal_fetch(wslot * PBL_WAVE + lane, s_c0, s_d4, s_q4);
     }
 
@@ -584,15 +624,57 @@ __global__ __launch_bounds__(WPB * PBL_WAVE, 1) void pbl_gemv_kernel(GemvArgs ar
             word_step<MB>(t[i], c_one, xr, acc, xl);
         }
     };
-    // The load for panel p + 2 is requested before panel p's arithmetic; the rotation below copies into the register of that load,
-    // hipcc waits vmcnt(0) in front of the copy, and so the prefetch is one panel deep (1 KiB per wave in flight).  A static
-    // three-set ring with a true two-panel lookahead measured equal at 6 instead of 8 waves per SIMD (profiles/r03_gemv_ring.md).
-    for (int p = wslot; p < P; p += WSTEP) {
-        u32x4 tn = t1;
-        if (p + 2 * WSTEP < P) tn = __builtin_nontemporal_load(tiles + (p + 2 * WSTEP) * 64);
-        panel(t0, p);
-        t0 = t1;
-        t1 = tn;
+    if constexpr (D == 2) {
+        // The load for panel p + 2 is requested before panel p's arithmetic; the rotation below copies into the register of that
+        // load, hipcc waits vmcnt(0) in front of the copy, and so the prefetch is one panel deep (1 KiB per wave in flight).
+        for (int p = wslot; p < P; p += WSTEP) {
+            u32x4 tn = t1;
+            if (p + 2 * WSTEP < P) tn = __builtin_nontemporal_load(tiles + (p + 2 * WSTEP) * 64);
+            panel(t0, p);
+            t0 = t1;
+            t1 = tn;
+        }
+    } else {
+        // Three panels per trip over the ring's three sets (the inner loop is unrolled, so h is a constant and no tile register is
+        // ever copied): the panel waits for its own set, requests the panel two steps on into the set its predecessor has just
+        // released, and computes.  The wait is a counted one: the request for the next panel stays outstanding behind it, so a
+        // tile has two panels of arithmetic to arrive in.  The ring holds the three sets the rotation above allocates anyway (its
+        // t0, t1 and tn); the ring of profiles/r03_gemv_ring.md had no pin in unpack_pair, cost 74 VGPRs and two waves per SIMD.
+        //
+        // The counted wait needs requests that are NOT conditional: where a request sits under a test, hipcc's own wait insertion
+        // has to assume that it may not have been issued, takes the set in use for the newest request and adds vmcnt(0) at its
+        // first use, behind the new request.  So whole trips in which every request exists run first, with nothing under a test;
+        // the last one to four panels run in the second loop, which drains the counter before each request and so looks one panel
+        // ahead, as the rotation does.  (The loads requested before phase 0 have landed -- the staging loops waited for x,
+        // requested behind them -- but they sit under tests; the drain in front of the loop takes them out of hipcc's books.  The
+        // scheduling barrier keeps hipcc from sinking the request below the panel's arithmetic.)
+        //
+        // INVARIANT behind vmcnt(1): panel() issues no vector-memory operation (x comes from LDS), so the only requests of this
+        // wave between two waits are the tile loads, one per panel.  A global load or store added to panel() would be the newest
+        // request at the next wait, which then means "all tiles landed": still correct (hipcc adds its own waits for what it
+        // loads), but the lookahead would silently be one panel again.
+        wait_vmcnt<0>();
+        int p0 = wslot;
+        for (; p0 + 4 * WSTEP < P; p0 += 3 * WSTEP) {
+#pragma unroll
+            for (int h = 0; h < 3; ++h) {
+                wait_vmcnt<1>();
+                t[(h + 2) % 3] = tile_fetch(p0 + (h + 2) * WSTEP);
+                __builtin_amdgcn_sched_barrier(0);
+                panel(t[h], p0 + h * WSTEP);
+            }
+        }
+        for (; p0 < P; p0 += 3 * WSTEP) {
+#pragma unroll
+            for (int h = 0; h < 3; ++h) {
+                const int p = p0 + h * WSTEP;
+                if (h && p >= P) break;
+                wait_vmcnt<0>();
+                if (p + 2 * WSTEP < P) t[(h + 2) % 3] = tile_fetch(p + 2 * WSTEP);
+                __builtin_amdgcn_sched_barrier(0);
+                panel(t[h], p);
+            }
+        }
     }
 
     // row-owner lanes: lane l owns row rho(l) (4 lanes per row).  Their row parameters are requested here, in front of the

@@ -4,6 +4,11 @@ M = 1 and M = 4, as the library in use computes them on the GPU.
 
     PBL_LIB=/path/to/libpbl.so-of-the-recording-commit  tools/record_gemv_golden.py [--out tests/golden] [--commit de42e4d]
 
+--cases MODULE records another case module of tests/ instead (gemv_lookahead_cases: tests/test_gpu_gemv_lookahead.py).  A case
+module has LAUNCHES, MS, pack_sets, build_group, fixture_name and SENTINEL as gemv_persistent_cases does; it may name its sidecar
+(SIDECAR) and its recording commit (COMMIT, the default of --commit), and may add single-layer launches (SPLITS with build_split,
+run_split, split_fixture_name and activations), recorded one [M, N] block per file.
+
 The committed fixtures were recorded with the library built from commit de42e4d (the parent of the change that reworked the
 kernel's salient rounds); PBL_LIB selects that build, the in-tree library is used when it is unset.  Per (launch, M) one
 tests/golden/<fixture_name>.npy holds the first `period` members' outputs back to back (fp16), and gemv_grouped_parent.json the
@@ -25,9 +30,13 @@ sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--commit", default="de42e4d", help="the commit the library in use was built from (goes into the sidecar)")
+    ap.add_argument("--commit", default=None, help="the commit the library in use was built from (goes into the sidecar); "
+                    "default: the case module's COMMIT, de42e4d for gemv_persistent_cases")
+    ap.add_argument("--cases", default="gemv_persistent_cases", help="the case module of tests/ to record")
     a = ap.parse_args()
-    import gemv_persistent_cases as GC
+    import importlib
+    GC = importlib.import_module(a.cases)
+    a.commit = a.commit or getattr(GC, "COMMIT", "de42e4d")
     from pb_llm_amd import _lib
     _lib.lib()
     os.makedirs(a.out, exist_ok=True)
@@ -52,7 +61,23 @@ def main():
             np.save(os.path.join(a.out, name), flat)
             side["files"][name] = {"sha256": hashlib.sha256(flat.tobytes()).hexdigest(), "elements": int(flat.size)}
             print(name, flat.size, "fp16 values")
-    with open(os.path.join(a.out, "gemv_grouped_parent.json"), "w") as f:
+    for sp in getattr(GC, "SPLITS", ()):
+        _, p = GC.build_split(sp)
+        pd = p.to("cuda:0")
+        for M in GC.MS:
+            x = torch.from_numpy(GC.activations(sp.K, M, 0)).to("cuda:0")
+            y, buf, keep = GC.run_split(pd, x, M)
+            torch.cuda.synchronize()
+            assert bool((buf[keep] == GC.SENTINEL).all()), (sp.name, M, "a store outside the layer's rows")
+            _, again, _ = GC.run_split(pd, x, M)
+            torch.cuda.synchronize()
+            assert torch.equal(buf.view(torch.int16), again.view(torch.int16)), (sp.name, M, "two launches differ")
+            flat = y.cpu().numpy().reshape(-1)
+            name = GC.split_fixture_name(sp, M) + ".npy"
+            np.save(os.path.join(a.out, name), flat)
+            side["files"][name] = {"sha256": hashlib.sha256(flat.tobytes()).hexdigest(), "elements": int(flat.size)}
+            print(name, flat.size, "fp16 values")
+    with open(os.path.join(a.out, getattr(GC, "SIDECAR", "gemv_grouped_parent.json")), "w") as f:
         json.dump(side, f, indent=1, sort_keys=True)
         f.write("\n")
 
