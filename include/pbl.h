@@ -553,9 +553,18 @@ int pbl_decode_attn_f16(const void* q, const int64_t* q_stride, const void* k_ca
  *      min(p + S, max_len) are never used, whatever they hold (NaN included).
  *   3. out [B S, ldo] fp16, row b S + s, head h at column h D (pbl_decode_attn_f16's layout).
  *   4. *pos += S, by a one-thread launch after everything that reads it.
+ * In 1. and 2. a negative *pos counts as 0 and one beyond max_len as max_len (p = clamp(*pos, 0, max_len): at max_len nothing is
+ * appended and every row attends to the whole cache); 4. advances the unclamped value.
  * Numerics: scores are fp32 sums of fp16 products on the matrix cores (v_mfma_f32_32x32x16_f16); the online softmax runs in fp32 over
- * key tiles; P is rounded to fp16 for the P V product and the denominator is summed from the ROUNDED P; the accumulator is fp32 and
- * acc / l is rounded to fp16 once.  Key tiles (64 rows) are laid from absolute key row 0 in every launch, so a query row's result
+ * key tiles; P = exp2(x - m_p), m_p = fl(m - 14) -- the running maximum m sits at 2^14, not at 1 -- is rounded to fp16 for the P V
+ * product and the denominator is summed from the ROUNDED P; the rescale factor between tiles is exp2(m_p_old - m_p_new), so the
+ * factor 2^(m - m_p) cancels in acc / l whatever the rounding of m - 14; the accumulator is fp32 and acc / l is rounded to fp16 once.
+ * With the offset a weight keeps fp16's full precision down to 2^-28 of its row's maximum (2^-14 without it: an attention sink 10
+ * or more above thousands of later keys put all of them on the subnormal grid, an error of the same sign on every key), lands on
+ * the subnormal grid below that and is dropped below 2^-39.  m - m_p is 14 to within half of fp32's spacing at m: 14 +- 2^-20 for
+ * |m| < 16, never above 15 while |m - 14| < 2^25; where the rounded difference would exceed 15 (base-2 scores of 2^25 and more, whose
+ * own spacing is 4) the offset is dropped (m_p = m), so P never exceeds 2^15 < 65504.  The fp32 sums stay below 2^31 max |v| at
+ * 65536 keys.  Key tiles (64 rows) are laid from absolute key row 0 in every launch, so a query row's result
  * depends only on its own q, its keys and that tiling -- not on which rows share its query tile, on S, or on how a prompt was
  * chunked.  No atomics, fixed order: bit-stable from run to run, eager or replayed.
  * PBL_ERR_INVALID_ARG before any device work for NULL pointers, sizes < 1, negative strides, ldo < Hq D, S > max_len, B Hkv max_len D

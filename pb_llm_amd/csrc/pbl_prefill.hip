@@ -20,8 +20,15 @@
 // 4 h + (j & 3): the V^T operand is read from LDS in that k order (two 8-byte key groups per step).
 //
 // Numerics.  Scores are fp32 sums of fp16 products on the matrix cores.  The online softmax runs in fp32 over the key tiles (base 2:
-// score x scaling x log2 e).  P is rounded to fp16 for the P V product and the denominator is summed from the ROUNDED P.  The
-// accumulator is fp32; acc / l is rounded to fp16 once.  A fully masked tile is an exact no-op (p = 0, rescale factor 1), so a query
+// score x scaling x log2 e).  P is rounded to fp16 for the P V product and the denominator is summed from the ROUNDED P.  P, l and
+// the accumulator are kept relative to m_p = fl(m - 14), not to the running maximum m: P = exp2(x - m_p), the rescale factor is
+// exp2(m_p_old - m_p_new), and acc / l is free of the factor however m - 14 was rounded in each tile.  fp16 is normal down to 2^-14,
+// so with the maximum at 1 every weight below 2^-14 of it lost precision and every one below 2^-25 vanished -- behind an attention
+// sink that is thousands of keys, all rounded the same way (far outside the float64 bound of the tests; measured in DESIGN.md).
+// The offset moves those two edges to 2^-28 and 2^-39.  m - m_p is 14 to within half of fp32's spacing at m (2^-20 for |m| < 16) and
+// at most 15 while |m - 14| < 2^25; beyond, where the spacing is 4 or more and the difference could come out as 16, the offset is
+// dropped for that tile (m_p = m).  So P <= 2^15 < 65504 for every input, and the fp32 sums stay below 2^31 max |v| at 65536 keys.
+// The accumulator is fp32; acc / l is rounded to fp16 once.  A fully masked tile is an exact no-op (p = 0, rescale factor 1), so a query
 // row's result depends only on its own q, its keys and the 64-key tiling from row 0 -- not on which rows share its query tile, on S,
 // or on how a prompt was chunked.  No atomics, fixed order: bit-stable from run to run, eager or replayed.
 //

@@ -19,6 +19,7 @@ constexpr int PF_THREADS = 256;
 constexpr int PF_TQ = 128;                     // query rows per workgroup, 32 per wave
 constexpr int PF_TK = 64;                      // keys per tile, laid from absolute key row 0
 constexpr float PF_LOG2E = 1.4426950408889634f;
+constexpr float PF_P_OFFSET = 14.f;            // P = exp2(x - fl(m - 14)): the row's maximum at 2^14 (pbl_prefill.hip, Numerics)
 
 struct PrefillArgs {
     const uint16_t* q;              // element (b, h, s, d) at b * q_sb + h * q_sh + s * q_ss + d
@@ -217,6 +218,7 @@ __global__ __launch_bounds__(PF_THREADS) void pbl_prefill_attn_kernel(Args a) {
 #pragma unroll
         for (int g = 0; g < 16; ++g) o[db][g] = 0.f;
     float m = -INFINITY, l = 0.f;                           // running max (base-2 scores) and this lane half's share of the sum
+    float m_p = -INFINITY;                                  // what P, l and o are relative to: m - 14, rounded (below)
 
     load_tile(0);
     for (int t = 0; t < nt; ++t) {
@@ -250,15 +252,22 @@ __global__ __launch_bounds__(PF_THREADS) void pbl_prefill_attn_kernel(Args a) {
             }
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         const float m_new = fmaxf(m, mx);                   // finite from tile 0 on: key 0 is valid for every row
-        const float alpha = __builtin_amdgcn_exp2f(m - m_new);
         m = m_new;
+        // P, l and o are kept relative to m_p = fl(m - 14), not to m: fp16's normal range then reaches down to 2^-28 of the row's
+        // maximum.  The subtraction is rounded to fp32; where that rounding would put the maximum above 2^15 (|m - 14| >= 2^25: fp32's
+        // spacing is 4 or more) the offset is dropped, so P <= 2^15 < 65504 whatever the scores.  alpha comes from the same m_p, so
+        // every tile's contribution is scaled by 2^-m_p exactly, however the rounding falls from tile to tile.
+        float m_p_new = m_new - PF_P_OFFSET;
+        if (m_new - m_p_new > PF_P_OFFSET + 1.f) m_p_new = m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m_p - m_p_new);
+        m_p = m_p_new;
         v8h pf[2][2];
         float lsum = 0.f;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const _Float16 ph = _Float16(__builtin_amdgcn_exp2f(x[kb][g] - m_new));
+                const _Float16 ph = _Float16(__builtin_amdgcn_exp2f(x[kb][g] - m_p));
                 pf[kb][g >> 3][g & 7] = ph;
                 lsum += float(ph);                          // the denominator sees what the product sees
             }

@@ -38,9 +38,9 @@ def position(pos):
     return torch.tensor(pos, dtype=torch.int64, device=DEV)
 
 
-def check_case(q, k_new, v_new, base_k, base_v, pos, scaling, what):
-    """one call at `pos` over a cache whose rows >= pos + S are NaN: the float64 and SDPA bounds, the position, the appended rows'
-    bits, the rows below (unchanged) and above (still NaN)"""
+def check_case(q, k_new, v_new, base_k, base_v, pos, scaling, what, sdpa=True):
+    """one call at `pos` over a cache whose rows >= pos + S are NaN: the float64 and (unless sdpa=False) SDPA bounds, the position,
+    the appended rows' bits, the rows below (unchanged) and above (still NaN)"""
     S, D = q.shape[2], q.shape[3]
     kc, vc = base_k.clone(), base_v.clone()
     kc[:, :, pos + S:] = float("nan")
@@ -53,7 +53,8 @@ def check_case(q, k_new, v_new, base_k, base_v, pos, scaling, what):
     full_k[:, :, pos:pos + S] = k_new
     full_v[:, :, pos:pos + S] = v_new
     within_ulps(out, ref64(q, full_k, full_v, pos, scaling), D, f"{what} vs float64")
-    within_ulps(out, sdpa16(q, full_k, full_v, pos, scaling), D, f"{what} vs SDPA")
+    if sdpa:
+        within_ulps(out, sdpa16(q, full_k, full_v, pos, scaling), D, f"{what} vs SDPA")
     for c, new, base in ((kc, k_new, base_k), (vc, v_new, base_v)):
         assert torch.equal(bits(c[:, :, pos:pos + S]), bits(new)), f"{what}: appended rows"
         assert torch.equal(bits(c[:, :, :pos]), bits(base[:, :, :pos])), f"{what}: rows below pos"
