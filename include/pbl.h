@@ -575,6 +575,28 @@ int pbl_prefill_attn_f16(const void* q, const int64_t* q_stride, const void* k_n
                          const int64_t* v_stride, void* k_cache, void* v_cache, int B, int S, int Hq, int Hkv, int D, int max_len,
                          float scaling, int64_t* pos, void* out, uint32_t ldo, void* stream);
 
+/* Branch attention over the same static KV cache (csrc/pbl_branch.hip; scoring.loglikelihood(share_prefix=True) through
+ * fusion._prefill_layer_forward): pbl_prefill_attn_f16 for S rows that are one shared context followed by the rows of several
+ * continuations, [ trunk | branch 0 | branch 1 | ... | padding ].  Two more DEVICE arguments: trunk, int32 [B], and lo, int32 [B, S]
+ * contiguous -- lo[b, s] the packed index of the first row of row s's own branch (0 for a trunk row, s for a padding row).
+ *   1., 3. and 4. are pbl_prefill_attn_f16's: the append to cache rows [p, p + S), the layout of out, *pos += S.
+ *   2. query row s attends to absolute key k iff  k <= min(p + s, max_len - 1)  and  ( k < p + trunk[b]  or  k >= p + lo[b, s] ):
+ *      the context and its own continuation, nothing of its siblings.
+ * Callers pass trunk >= 1.  The tables cannot break the kernel, whatever they hold: lo[b, s] is clamped to [0, s] and p + trunk[b] to
+ * [1, max_len], so key 0 is seen by every row (the online softmax needs one finite score in tile 0) and no read leaves the valid rows;
+ * trunk < 1 at p = 0 behaves as trunk = 1.
+ * The kernel is pbl_prefill_attn_f16's (same tiles, same fp16 P relative to m - 14, same fixed order, no atomics, no workspace) with
+ * the two comparisons added to the causal test: with lo = 0 everywhere the result equals pbl_prefill_attn_f16's bit for bit, and a
+ * row's result depends only on its own q, the keys it sees and the 64-key tiling from row 0.  A key a row does not see contributes
+ * exactly nothing whatever it holds: its score is replaced by -inf, and Inf / NaN VALUE elements enter the product as +0 in this entry
+ * (0 x NaN is NaN on the matrix cores, and one V tile serves rows that see a key and rows that do not); a NaN KEY row still gives NaN
+ * in every row that sees it.
+ * Checks, scope and error codes of pbl_prefill_attn_f16, plus PBL_ERR_INVALID_ARG for a NULL table or a table that overlaps an output
+ * (caches, out, pos).  fp16 cache only.  Three launches, capturable; one graph serves every position and every table contents. */
+int pbl_branch_attn_f16(const void* q, const int64_t* q_stride, const void* k_new, const int64_t* k_stride, const void* v_new,
+                        const int64_t* v_stride, void* k_cache, void* v_cache, const int32_t* trunk, const int32_t* lo, int B, int S,
+                        int Hq, int Hkv, int D, int max_len, float scaling, int64_t* pos, void* out, uint32_t ldo, void* stream);
+
 /* The FP8 KV cache (csrc/pbl_kv8.hip; harness.DecodeSession(..., kv_cache="fp8") / harness.generate(..., kv_cache="fp8")): the three
  * entries above over a cache that takes half the bytes.
  *   The format.  A cache row -- one token of one kv head, D = 64 or 128 values -- is D bytes of OCP e4m3fn and ONE power-of-two scale:

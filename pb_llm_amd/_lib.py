@@ -65,7 +65,7 @@ EXPORTS = ["pbl_status_string", "pbl_version", "pbl_pack_dense_f32", "pbl_pack_d
            "pbl_rope_append_f16", "pbl_decode_attn_workspace_bytes", "pbl_decode_attn_f16", "pbl_prefill_attn_f16", "pbl_select_token_f16",
            "pbl_select_token_minp_f16", "pbl_process_logits_f16",
            "pbl_score_tokens_f16", "pbl_gemv_route", "pbl_spec_verify_f16", "pbl_ngram_draft",
-           "pbl_rope_append_kv8", "pbl_decode_attn_kv8", "pbl_prefill_attn_kv8"]
+           "pbl_rope_append_kv8", "pbl_decode_attn_kv8", "pbl_prefill_attn_kv8", "pbl_branch_attn_f16"]
 
 
 def lib() -> C.CDLL:
@@ -245,6 +245,9 @@ def lib() -> C.CDLL:
     L.pbl_prefill_attn_f16.restype = C.c_int
     L.pbl_prefill_attn_f16.argtypes = [vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, vp, C.c_int,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, u32, vp]
+    L.pbl_branch_attn_f16.restype = C.c_int
+    L.pbl_branch_attn_f16.argtypes = [vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64), vp, vp, vp, vp,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, u32, vp]
     L.pbl_rope_append_kv8.restype = C.c_int
     L.pbl_rope_append_kv8.argtypes = [vp, u32, u32, u32, u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64,
                                       C.c_int64, vp, C.POINTER(C.c_int64), vp, vp, vp, vp, C.c_int, vp, vp]

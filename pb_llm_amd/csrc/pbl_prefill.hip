@@ -45,18 +45,7 @@ int pbl_prefill_attn_f16(const void* q, const int64_t* q_stride, const void* k_n
     if (rc != PBL_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
 
-    AppendArgs ap{};
-    ap.k = static_cast<const uint16_t*>(k_new); ap.v = static_cast<const uint16_t*>(v_new);
-    ap.kc = static_cast<uint16_t*>(k_cache); ap.vc = static_cast<uint16_t*>(v_cache);
-    ap.pos = pos;
-    ap.k_sb = k_stride[0]; ap.k_sh = k_stride[1]; ap.k_ss = k_stride[2];
-    ap.v_sb = v_stride[0]; ap.v_sh = v_stride[1]; ap.v_ss = v_stride[2];
-    ap.S = S; ap.Hkv = Hkv; ap.D = D; ap.max_len = max_len;
-    ap.k_vec = pf_vec(k_new, k_stride); ap.v_vec = pf_vec(v_new, v_stride);
-    void* apv[] = {&ap};
-    const unsigned ablocks = unsigned((int64_t(S) * (D / 8) + PF_THREADS - 1) / PF_THREADS);
-    if (hipLaunchKernel(reinterpret_cast<const void*>(pbl_prefill_append_kernel), dim3(ablocks, Hkv, B), dim3(PF_THREADS), apv, 0, st) != hipSuccess)
-        return PBL_ERR_LAUNCH;
+    if (prefill_append(k_new, k_stride, v_new, v_stride, k_cache, v_cache, B, S, Hkv, D, max_len, pos, st) != PBL_OK) return PBL_ERR_LAUNCH;
 
     PrefillArgs a{};
     return prefill_attend(a, q, q_stride, k_cache, v_cache, B, S, Hq, Hkv, D, max_len, scaling, pos, out, ldo, st);

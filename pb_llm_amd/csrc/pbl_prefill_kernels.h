@@ -1,7 +1,9 @@
 // pbl_prefill_kernels.h -- the kernels and launch helpers of the causal prefill attention, shared by its two cache formats: fp16 rows
 // (pbl_prefill.hip, pbl_prefill_attn_f16; the design is described there) and FP8 rows with one power-of-two scale each (pbl_kv8.hip,
 // pbl_prefill_attn_kv8).  pbl_prefill_attn_kernel is ONE template: the cache format changes how a tile's rows come out of global
-// memory (PrefillChunk) and nothing else -- the LDS layouts, the products, the softmax and the store exist once.
+// memory (PrefillChunk) and nothing else -- the LDS layouts, the products, the softmax and the store exist once.  Which keys at or
+// below a row's diagonal it sees is a mask policy: CausalMask (all of them: the two prefill entries) or BranchMask (pbl_branch.hip,
+// pbl_branch_attn_f16: the rows of several continuations packed behind one shared context).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -37,6 +39,11 @@ struct PrefillArgs {
 struct PrefillArgsKv8 : PrefillArgs {
     const float* ksc;               // [B, Hkv, max_len]: the power-of-two scale of each K / V row
     const float* vsc;
+};
+
+struct PrefillArgsBranch : PrefillArgs {
+    const int32_t* trunk;           // [B]: keys below p + trunk[b] are seen by every row of batch entry b
+    const int32_t* lo;              // [B, S]: row s also sees keys from p + lo[b, s] on (its own branch), up to its diagonal
 };
 
 template <typename Args> struct prefill_is_kv8 { static constexpr bool value = false; };
@@ -119,8 +126,45 @@ template <> struct PrefillChunk<true> {
     __device__ __forceinline__ uint4 halves() const { return kv8_to_halves(w, scale); }
 };
 
-// Args: PrefillArgs (fp16 cache) or PrefillArgsKv8 (FP8 cache: only the tile loader differs)
-template <int D, typename Args>
+// The mask policy: which keys at or below its diagonal a query row sees.  CausalMask: all of them -- nothing is computed, the kernel is
+// what it was before the policy existed.
+struct CausalMask {
+    static constexpr bool finite_v = false;
+    template <typename Args> __device__ __forceinline__ void init(const Args&, int, int, bool, int64_t) {}
+    __device__ __forceinline__ bool sees(int) const { return true; }
+};
+
+// BranchMask: key k iff k < p + trunk[b] (the shared context) or k >= p + lo[b, s] (the row's own branch).  The tables are made safe
+// here: lo is clamped to [0, s] (a row always sees itself, and no index leaves [p, p + S)), p + trunk to [1, max_len] -- key 0 is
+// seen by every row whatever the tables hold, which the online softmax relies on (the running maximum is finite from tile 0).
+// Kept as tr = p + trunk and gap = the number of keys from tr on that the row does NOT see (0 where its branch starts at or below
+// tr): key k is seen iff unsigned(k - tr) >= gap -- one subtraction and one comparison per score.
+struct BranchMask {
+    static constexpr bool finite_v = true;
+    int tr;
+    unsigned gap;
+    __device__ __forceinline__ void init(const PrefillArgsBranch& a, int b, int sq, bool q_ok, int64_t p) {
+        int64_t t = p + int64_t(a.trunk[b]);
+        tr = int(t < 1 ? 1 : (t > a.max_len ? int64_t(a.max_len) : t));
+        int l = q_ok ? a.lo[size_t(b) * a.S + sq] : 0;
+        l = l < 0 ? 0 : (l > sq ? sq : l);
+        const int64_t la = p + l;
+        gap = la > tr ? unsigned(la - tr) : 0u;
+    }
+    __device__ __forceinline__ bool sees(int key) const { return unsigned(key - tr) >= gap; }
+};
+
+// 8 halves with every Inf / NaN among them replaced by +0 (BranchMask's V tiles: a masked probability is 0, but 0 x NaN = NaN inside
+// an MFMA, and a V tile is shared by rows that see a key and rows that do not)
+__device__ __forceinline__ uint4 finite_halves(uint4 w) {
+    auto flags = [](uint32_t x) { return ((x & 0x7c007c00u) + 0x04000400u) & 0x80008000u; };   // bit 15 of a half: exponent all ones
+    if ((flags(w.x) | flags(w.y) | flags(w.z) | flags(w.w)) == 0) return w;
+    auto clear = [&](uint32_t x) { const uint32_t f = flags(x); return x & ~((f - (f >> 15)) | f); };
+    return make_uint4(clear(w.x), clear(w.y), clear(w.z), clear(w.w));
+}
+
+// Args: PrefillArgs (fp16 cache), PrefillArgsKv8 (FP8 cache: only the tile loader differs) or PrefillArgsBranch (with BranchMask)
+template <int D, typename Args, typename Mask = CausalMask>
 __global__ __launch_bounds__(PF_THREADS) void pbl_prefill_attn_kernel(Args a) {
     constexpr bool KV8 = prefill_is_kv8<Args>::value;
     constexpr int KS = D / 16;                             // k-steps of the first product
@@ -153,6 +197,8 @@ __global__ __launch_bounds__(PF_THREADS) void pbl_prefill_attn_kernel(Args a) {
     const int64_t lim64 = p + sq < a.max_len - 1 ? p + sq : int64_t(a.max_len - 1);
     const int lim = int(lim64);                             // its last key
     const size_t kvbase = (size_t(b) * a.Hkv + hk) * a.max_len;
+    Mask mask;
+    mask.init(a, b, sq, q_ok, p);
 
     v8h qf[KS];
     {
@@ -198,7 +244,8 @@ __global__ __launch_bounds__(PF_THREADS) void pbl_prefill_attn_kernel(Args a) {
             uint32_t u[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const uint4 w = vreg[i].halves();
+                uint4 w = vreg[i].halves();
+                if constexpr (Mask::finite_v) w = finite_halves(w);
                 u[i][0] = w.x; u[i][1] = w.y; u[i][2] = w.z; u[i][3] = w.w;
             }
 #pragma unroll
@@ -246,7 +293,7 @@ __global__ __launch_bounds__(PF_THREADS) void pbl_prefill_attn_kernel(Args a) {
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
                 const int key = k0 + 32 * kb + (g & 3) + 8 * (g >> 2) + 4 * hh;
-                const float sc = key <= lim ? x[kb][g] * a.scale_log2 : -INFINITY;
+                const float sc = key <= lim && mask.sees(key) ? x[kb][g] * a.scale_log2 : -INFINITY;
                 x[kb][g] = sc;
                 mx = fmaxf(mx, sc);
             }
@@ -361,9 +408,26 @@ int prefill_check(const void* q, const int64_t* q_stride, const void* k_new, con
     return PBL_OK;
 }
 
+// the fp16 cache's append launch: k_new / v_new bit for bit into cache rows [p, p + S)
+int prefill_append(const void* k_new, const int64_t* k_stride, const void* v_new, const int64_t* v_stride, void* k_cache, void* v_cache,
+                   int B, int S, int Hkv, int D, int max_len, const int64_t* pos, hipStream_t st) {
+    AppendArgs ap{};
+    ap.k = static_cast<const uint16_t*>(k_new); ap.v = static_cast<const uint16_t*>(v_new);
+    ap.kc = static_cast<uint16_t*>(k_cache); ap.vc = static_cast<uint16_t*>(v_cache);
+    ap.pos = pos;
+    ap.k_sb = k_stride[0]; ap.k_sh = k_stride[1]; ap.k_ss = k_stride[2];
+    ap.v_sb = v_stride[0]; ap.v_sh = v_stride[1]; ap.v_ss = v_stride[2];
+    ap.S = S; ap.Hkv = Hkv; ap.D = D; ap.max_len = max_len;
+    ap.k_vec = pf_vec(k_new, k_stride); ap.v_vec = pf_vec(v_new, v_stride);
+    void* apv[] = {&ap};
+    const unsigned ablocks = unsigned((int64_t(S) * (D / 8) + PF_THREADS - 1) / PF_THREADS);
+    return hipLaunchKernel(reinterpret_cast<const void*>(pbl_prefill_append_kernel), dim3(ablocks, Hkv, B), dim3(PF_THREADS), apv, 0, st) == hipSuccess
+               ? PBL_OK : PBL_ERR_LAUNCH;
+}
+
 // the attention launch over the cache rows that the entry's append launch has written, and the advance of *pos; the caller has put
 // into `a` what its cache format adds to PrefillArgs
-template <typename Args>
+template <typename Mask = CausalMask, typename Args>
 int prefill_attend(Args& a, const void* q, const int64_t* q_stride, const void* k_cache, const void* v_cache, int B, int S, int Hq,
                    int Hkv, int D, int max_len, float scaling, int64_t* pos, void* out, uint32_t ldo, hipStream_t st) {
     a.q = static_cast<const uint16_t*>(q);
@@ -377,8 +441,8 @@ int prefill_attend(Args& a, const void* q, const int64_t* q_stride, const void* 
     a.q_vec = pf_vec(q, q_stride);
     a.o_vec = reinterpret_cast<uintptr_t>(out) % 8 == 0 && ldo % 4 == 0;
     void* argv[] = {&a};
-    const void* kern = D == 64 ? reinterpret_cast<const void*>(pbl_prefill_attn_kernel<64, Args>)
-                               : reinterpret_cast<const void*>(pbl_prefill_attn_kernel<128, Args>);
+    const void* kern = D == 64 ? reinterpret_cast<const void*>(pbl_prefill_attn_kernel<64, Args, Mask>)
+                               : reinterpret_cast<const void*>(pbl_prefill_attn_kernel<128, Args, Mask>);
     if (hipLaunchKernel(kern, dim3((S + PF_TQ - 1) / PF_TQ, Hq, B), dim3(PF_THREADS), argv, 0, st) != hipSuccess) return PBL_ERR_LAUNCH;
     int S_arg = S;
     void* adv[] = {&pos, &S_arg};

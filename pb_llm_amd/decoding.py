@@ -38,11 +38,11 @@ def _decode_cache_layer(cache, layer_idx: int, batch: int, n_kv: int, head_dim: 
     return lay
 
 
-def _prefill_cache_layer(cache, layer_idx: int, batch: int, seq: int, n_q: int, n_kv: int, head_dim: int):
+def _prefill_cache_layer(cache, layer_idx: int, batch: int, seq: int, n_q: int, n_kv: int, head_dim: int, branch: bool = False):
     """_decode_cache_layer's counterpart for the prefill-attention branch (any batch, any number of rows): cache is a DecodeCache, its
     layer a plain, initialised StaticLayer of fp16 [batch, n_kv, max_len, head_dim] tensors that runtime.prefill_attention_ok takes
-    -- else None (HF's path)"""
-    if not PREFILL_ATTENTION or _DECODE_CACHE is None or not isinstance(cache, _DECODE_CACHE) or layer_idx is None \
+    -- else None (HF's path).  branch: the cache carries a branch table (_cache_branch): PREFILL_ATTENTION is not asked"""
+    if not (PREFILL_ATTENTION or branch) or _DECODE_CACHE is None or not isinstance(cache, _DECODE_CACHE) or layer_idx is None \
             or layer_idx >= len(cache.layers):
         return None
     from transformers.cache_utils import StaticLayer
@@ -53,6 +53,14 @@ def _prefill_cache_layer(cache, layer_idx: int, batch: int, seq: int, n_q: int, 
     if (B, H, D) != (batch, n_kv, head_dim) or not runtime.prefill_attention_ok(batch, seq, n_q, n_kv, head_dim, L):
         return None
     return lay
+
+
+def _cache_branch(cache):
+    """(trunk, lo), the branch table a scorer has set on a DecodeCache around one forward (scoring.loglikelihood(share_prefix=True);
+    runtime.branch_attention_f16's tables) -- else None"""
+    if _DECODE_CACHE is None or not isinstance(cache, _DECODE_CACHE):
+        return None
+    return cache.branch
 
 
 def _kv8_cache_layer(cache, layer_idx: int):
@@ -144,7 +152,10 @@ def _decode_cache_class():
             appends to it and attends over its valid rows with the HIP decode attention (runtime.rope_append_f16 /
             decode_attention_f16) instead -- and, with PREFILL_ATTENTION on, a prefill of more than 4 rows with
             runtime.prefill_attention_f16; those paths ignore the attention mask, hence the unpadded-batch contract.
-            kv_cache="fp8": every layer is a Kv8StaticLayer instead -- half the bytes, for folded layers only (DecodeSession checks)."""
+            kv_cache="fp8": every layer is a Kv8StaticLayer instead -- half the bytes, for folded layers only (DecodeSession checks).
+            branch: normally None.  scoring.loglikelihood(share_prefix=True) sets (trunk, lo) -- runtime.branch_attention_f16's tables
+            for the rows of the NEXT forward -- around one forward and clears it in a finally; folded layers then attend with
+            runtime.branch_attention_f16 whatever the row count, and a layer that cannot raises."""
 
             def __init__(self, config, batch: int, max_cache_len: int, device, dtype, kv_cache: str = "fp16"):
                 super().__init__(config=config, max_cache_len=max_cache_len)
@@ -159,6 +170,7 @@ def _decode_cache_class():
                 head_dim = getattr(text, "head_dim", None) or text.hidden_size // text.num_attention_heads
                 self.early_initialization(batch, text.num_key_value_heads, head_dim, dtype, torch.device(device))
                 self.batch = batch
+                self.branch = None
 
         DecodeCache.__qualname__ = "DecodeCache"
         _DECODE_CACHE = DecodeCache

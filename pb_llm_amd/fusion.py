@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import runtime
-from .decoding import _decode_cache_layer, _kv8_cache_layer, _prefill_cache_layer
+from .decoding import _cache_branch, _decode_cache_layer, _kv8_cache_layer, _prefill_cache_layer
 from .packing import concat_rows
 from .quant import PBLinear, tensor_version
 
@@ -224,7 +224,7 @@ def _mlp_tail(down: PBLinear, act_fn, gu: torch.Tensor, inter: int, residual: to
     return y if residual is None else residual + y.reshape(residual.shape)
 
 
-def _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings, kv8=None):
+def _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings, kv8=None, branch=None):
     """THE prefill-attention ladder of a folded layer (decoding.PREFILL_ATTENTION): more than 4 fp16 rows on the GPU without autograd,
     position_embeddings given, the layer not training and a DecodeCache layer that runtime.prefill_attention_ok takes -- else None,
     before anything ran, and the caller runs LlamaDecoderLayer.forward.  The layer as LlamaDecoderLayer / LlamaAttention compute it:
@@ -233,10 +233,12 @@ def _prefill_layer_forward(self, hidden_states, past_key_values, position_embedd
     which advances the layer's position on the device as StaticLayer.update would have), o_proj, the residual, the post norm, the
     MLP and the residual.  The attention mask is not used: DecodeCache's unpadded-batch contract.
     kv8: the layer's FP8 cache layer (decoding._kv8_cache_layer) -- the attention is then runtime.prefill_attention_kv8 whatever
-    PREFILL_ATTENTION says, and a shape it declines is an error: there is no other path over that cache."""
+    PREFILL_ATTENTION says, and a shape it declines is an error: there is no other path over that cache.
+    branch: the cache's branch table (decoding._cache_branch) -- any number of rows then qualifies, PREFILL_ATTENTION is not asked and
+    the attention is runtime.branch_attention_f16 (the caller turns None into an error: no other path applies the table)."""
     x = hidden_states
     attn = self.self_attn
-    if position_embeddings is None or x.dim() != 3 or x.shape[0] * x.shape[1] <= 4 or not x.is_cuda or x.dtype != torch.float16 \
+    if position_embeddings is None or x.dim() != 3 or (branch is None and x.shape[0] * x.shape[1] <= 4) or not x.is_cuda or x.dtype != torch.float16 \
             or (torch.is_grad_enabled() and x.requires_grad) or self.training or attn.training:
         return None
     B, S, _ = x.shape
@@ -247,7 +249,7 @@ def _prefill_layer_forward(self, hidden_states, past_key_values, position_embedd
             raise RuntimeError(f"the FP8 KV cache declines batch {B}, {S} rows, heads {n_q} / {n_kv} x {D} (runtime.kv8_ok)")
         lay = kv8
     else:
-        lay = _prefill_cache_layer(past_key_values, attn.layer_idx, B, S, n_q, n_kv, D)
+        lay = _prefill_cache_layer(past_key_values, attn.layer_idx, B, S, n_q, n_kv, D, branch=branch is not None)
     if lay is None:
         return None
     from transformers.models.llama import modeling_llama as ML
@@ -262,6 +264,8 @@ def _prefill_layer_forward(self, hidden_states, past_key_values, position_embedd
     if kv8 is not None:
         a = runtime.prefill_attention_kv8(rot[0], rot[1], v, lay.keys, lay.values, lay.key_scales, lay.value_scales,
                                           lay.cumulative_length, attn.scaling)
+    elif branch is not None:
+        a = runtime.branch_attention_f16(rot[0], rot[1], v, lay.keys, lay.values, lay.cumulative_length, attn.scaling, *branch)
     else:
         a = runtime.prefill_attention_f16(rot[0], rot[1], v, lay.keys, lay.values, lay.cumulative_length, attn.scaling)
     if a is None:                           # (prefill_attention_ok / kv8_ok held for the cache layer)
@@ -280,13 +284,23 @@ def _folded_layer_forward(self, hidden_states, attention_mask=None, position_ids
     a DecodeCache).  Every other call runs LlamaDecoderLayer.forward (the prologues=True layer).
     Over an FP8 cache (DecodeSession(..., kv_cache="fp8")) the append and the attention are runtime.rope_append_kv8 +
     decode_attention_kv8 at <= 4 rows and runtime.prefill_attention_kv8 above; a call that cannot take these paths (autograd,
-    training, not fp16, no position_embeddings) raises RuntimeError: LlamaDecoderLayer.forward cannot read that cache."""
+    training, not fp16, no position_embeddings) raises RuntimeError: LlamaDecoderLayer.forward cannot read that cache.
+    Over a cache that carries a branch table (DecodeCache.branch, set by scoring.loglikelihood(share_prefix=True)): _prefill_layer_forward
+    with runtime.branch_attention_f16 for ANY number of rows; a call that cannot take it raises RuntimeError, because no other path
+    applies the table."""
     d_in = self.input_layernorm
     kv8 = _kv8_cache_layer(past_key_values, self.self_attn.layer_idx)
-    if position_embeddings is None or hidden_states.dim() != 3 or not _prologue_ok(hidden_states, d_in.norm.weight, stateless=True):
-        out = _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings, kv8)
+    branch = _cache_branch(past_key_values)
+    if branch is not None and kv8 is not None:
+        raise RuntimeError("branch attention reads the fp16 KV cache only: there is no FP8 variant")
+    if branch is not None or position_embeddings is None or hidden_states.dim() != 3 \
+            or not _prologue_ok(hidden_states, d_in.norm.weight, stateless=True):
+        out = _prefill_layer_forward(self, hidden_states, past_key_values, position_embeddings, kv8, branch)
         if out is not None:
             return out
+        if branch is not None:
+            raise RuntimeError("a folded layer over a cache with a branch table runs runtime.branch_attention_f16 only: fp16 activations "
+                               "on the GPU, no autograd, eval mode, position_embeddings and heads the entry takes are required")
         if kv8 is not None:
             raise RuntimeError("a folded layer over an FP8 KV cache runs its HIP paths only: fp16 activations on the GPU, no autograd, "
                                "eval mode and position_embeddings are required")

@@ -322,6 +322,41 @@ def prefill_attention_f16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_c
     return out
 
 
+def branch_attention_ok(batch: int, seq: int, n_q: int, n_kv: int, head_dim: int, max_len: int) -> bool:
+    """the scope of branch_attention_f16 (pbl_branch_attn_f16): prefill_attention_ok's"""
+    return prefill_attention_ok(batch, seq, n_q, n_kv, head_dim, max_len)
+
+
+def branch_attention_f16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                         pos: torch.Tensor, scaling: float, trunk: torch.Tensor, lo: torch.Tensor) -> torch.Tensor | None:
+    """prefill_attention_f16 for S rows packed as [ shared context | branch 0 | branch 1 | ... | padding ] (pbl_branch_attn_f16): the
+    same arguments, contract and result, plus trunk (int32 [B], >= 1: the context's rows) and lo (int32 [B, S] contiguous: the packed
+    index of the first row of row s's own branch; 0 for a context row, s for a padding row), both on q's device.  Query row s attends
+    to cache row k iff k <= pos + s and (k < pos + trunk[b] or k >= pos + lo[b, s]).  None where the entry declines
+    (branch_attention_ok); the cache and pos are then untouched."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 4 or t.dtype != torch.float16 or not t.is_cuda or t.device != q.device or t.stride(3) != 1 or min(t.stride()) < 0:
+            raise ValueError(f"branch_attention_f16: {name} must be an fp16 [B, H, S, D] GPU tensor with unit d stride")
+    B, Hq, S, D = (int(d) for d in q.shape)
+    Bc, Hkv, max_len, Dc = _cache_args(k_cache, v_cache, pos, q.device, "branch_attention_f16")
+    if (Bc, Dc) != (B, D) or tuple(k.shape) != (B, Hkv, S, D) or k.shape != v.shape:
+        raise ValueError("branch_attention_f16: k / v must be [B, Hkv, S, D] and the cache [B, Hkv, max_len, D] for q [B, Hq, S, D]")
+    for name, t, shape in (("trunk", trunk, (B,)), ("lo", lo, (B, S))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != q.device or not t.is_contiguous():
+            raise ValueError(f"branch_attention_f16: {name} must be a contiguous int32 {list(shape)} tensor on the activations' device")
+    if not branch_attention_ok(B, S, Hq, Hkv, D, max_len):
+        return None
+    out = torch.empty(B * S, Hq * D, dtype=torch.float16, device=q.device)
+    rc = _lib.lib().pbl_branch_attn_f16(q.data_ptr(), (C.c_int64 * 3)(*q.stride()[:3]), k.data_ptr(), (C.c_int64 * 3)(*k.stride()[:3]),
+                                        v.data_ptr(), (C.c_int64 * 3)(*v.stride()[:3]), k_cache.data_ptr(), v_cache.data_ptr(),
+                                        trunk.data_ptr(), lo.data_ptr(), B, S, Hq, Hkv, D, max_len, float(scaling), pos.data_ptr(),
+                                        out.data_ptr(), Hq * D, torch.cuda.current_stream(q.device).cuda_stream)
+    if rc == _lib.PBL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "branch attention")
+    return out
+
+
 # ---- the FP8 KV cache (csrc/pbl_kv8.hip; the format is stated in include/pbl.h) -------------------------------------------------------
 KV8_E_MIN, KV8_E_MAX, KV8_MAX = -15, 7, 448.0
 
